@@ -9,6 +9,10 @@ reduce (angle-wrapped deltas) and ONE all-reduce update the global model.  Nothi
 the timed region.  Total clients are fixed as N grows -> strong scaling.
 
 Usage: python bench.py [--gpus N --steps K --warmup W]   (N>1: launched by torch.distributed.run)
+
+A plain run sets up, runs W warm-up rounds, times K rounds and prints one JSON line.  ``--dump-outputs DIR`` also
+writes what the last timed round computed as ``DIR/<name>.npy``.  ``--full`` adds, after the timed rounds, the
+per-phase calibration rounds, the test-set evaluation and the MFMA-vs-fp32 precision check to that line.
 """
 from __future__ import annotations
 
@@ -55,11 +59,47 @@ def timed_rounds(cfg, device, backend, world, warmup: int, steps: int, counts: l
         runner.comm_bytes = rec.get("comm_bytes_per_rank", 0)
         if counts is not None:
             counts.append(rec["participants"] - rec["dropped"])
+        runner.last_record = rec            # the last timed round's unresolved record (dump_outputs reads it)
     # host time to build and enqueue a round, without the time it waited for the GPU to free a pinned buffer
     runner.host_ms = 1e3 * (time.perf_counter() - t0 - (_tr.WAIT_S[0] - w0)) / max(steps, 1)
     sync()
     dt = time.perf_counter() - t0
     return runner, max_over_ranks(dt, world)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def _capped(a, budget: int):
+    """``a`` itself while it fits ``budget`` bytes, else a fixed (seed 0) sample of its elements in index order."""
+    import numpy as np
+    if a.nbytes <= budget:
+        return a
+    idx = np.sort(np.random.default_rng(0).choice(a.size, size=budget // a.itemsize, replace=False))
+    return a.reshape(-1)[idx]
+
+
+def dump_outputs(runner, world, out_dir: str) -> None:
+    """Write what the last timed round handed its caller as ``out_dir/<name>.npy`` (rank 0; every rank holds the
+    same values after the round's all-reduce): ``global_params`` (float32) = the global model the round left in
+    ``runner.params``, ``round_metrics`` (float64) = the round record's device metrics, summed over all clients:
+    [loss sum, correct sum, samples, local steps, saturated fixed-point terms].  Call it right after
+    ``timed_rounds``, before anything else runs a round.  The data, the sampling and the initial model are keyed by
+    the config's seeds, so equal arguments give equal inputs in every run."""
+    import numpy as np
+    import torch
+    if runner.device.type == "cuda":
+        torch.cuda.synchronize()
+    arrays = {"global_params": runner.params.detach().float().cpu().numpy()}
+    rec = getattr(runner, "last_record", None)
+    if rec is not None and "_metrics" in rec:
+        arrays["round_metrics"] = rec["_metrics"].detach().double().cpu().numpy()
+    if not world.is_main:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BUDGET_BYTES // len(arrays)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), _capped(np.ascontiguousarray(a), budget))
 
 
 def phase_ms(runner, world, steps: int, calib: int = 5) -> dict:
@@ -181,8 +221,15 @@ def main():
                     help="mfma: fp16-state MFMA group-unitary engine (ops/hea_mfma.py); mfma_bf16: the same engine "
                          "with bf16 state storage; valu: fp32 pass engine")
     ap.add_argument("--precision-check", type=int, default=1,
-                    help="after timing, one untimed VJP on the fp32 VALU engine at the bench shape: report the "
-                         "MFMA engine's max abs <Z> / gradient differences (0 = skip)")
+                    help="with --full: after timing, one untimed VJP on the fp32 VALU engine at the bench shape: "
+                         "report the MFMA engine's max abs <Z> / gradient differences (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed rounds also run what the headline figure does not need: the per-phase "
+                         "calibration rounds (*_ms), the test-set evaluation (test_acc_after) and the precision "
+                         "check against the fp32 VALU engine (max_abs_err_*)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed rounds write what the last one computed (global model, round metrics) "
+                         "as DIR/<name>.npy")
     args = ap.parse_args()
     relaunch_if_needed(args.gpus)
 
@@ -193,13 +240,17 @@ def main():
     cfg = make_config(args)
     device, backend, world = setup(cfg)
     runner, dt = timed_rounds(cfg, device, backend, world, args.warmup, args.steps)
+    if args.dump_outputs:
+        dump_outputs(runner, world, args.dump_outputs)
     # clients trained by each rank (the 8-GPU operating point is 8 of the 64 headline clients per rank)
     from qfedx_amd.parallel.dist import all_gather_cat
     per_rank = [int(v) for v in all_gather_cat(torch.tensor([len(runner.local_ids)], dtype=torch.int64,
                                                              device=device), world).cpu().tolist()]
-    phases = phase_ms(runner, world, args.steps)
-    ev = runner.evaluate()
-    prec = precision_check(runner, args.batch) if (args.precision_check and device.type == "cuda") else {}
+    # --full only: everything below the timed rounds that takes runs of its own
+    phases = phase_ms(runner, world, args.steps) if args.full else {}
+    acc = {"test_acc_after": round(runner.evaluate()["test_acc"], 4)} if args.full else {}
+    prec = precision_check(runner, args.batch) if (args.full and args.precision_check
+                                                   and device.type == "cuda") else {}
     local_steps_total = args.clients * args.local_steps * args.steps
     value = local_steps_total / dt
     rounds_per_s = args.steps / dt
@@ -230,7 +281,7 @@ def main():
             "rounds_per_sec": round(rounds_per_s, 4),
             "samples_per_sec": round(value * args.batch, 1),
             "backend": backend,
-            "test_acc_after": round(ev["test_acc"], 4),
+            **acc,
             "dist_backend": world.backend,
             # ranks in the process group as torch.distributed sees it (0: no group) and whether the round's
             # all-reduce ran captured in the round hipGraph on every rank (agreed at startup; "mixed" if a later

@@ -11,8 +11,8 @@ step() {
   echo "$name rc=$rc"; grep '"metric"' "gpurun_out/$name.log" | cut -c1-220
   [ $rc -eq 0 ] || exit $rc
 }
-step share8 300 python bench.py --steps 30 --warmup 5 --clients 8
-step bench64 300 python bench.py --steps 20 --warmup 3
+step share8 300 python bench.py --full --steps 30 --warmup 5 --clients 8
+step bench64 300 python bench.py --full --steps 20 --warmup 3
 step prof8 300 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/prof8 -o share8 -- python3 bench.py --steps 20 --warmup 3 --clients 8
 step prof64 300 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/prof8 -o full64 -- python3 bench.py --steps 10 --warmup 3
 python3 scripts/round_timeline.py gpurun_out/prof8/share8_kernel_trace.csv

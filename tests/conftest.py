@@ -7,8 +7,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-REFERENCE = "/root/reference"
-
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs an MI355X GPU (HIP kernels)")
@@ -23,11 +21,6 @@ def pytest_collection_modifyitems(config, items):
     for it in items:
         if "gpu" in it.keywords:
             it.add_marker(skip)
-
-
-@pytest.fixture(scope="session")
-def reference_dir():
-    return REFERENCE if os.path.isdir(REFERENCE) else None
 
 
 @pytest.fixture(scope="session")

@@ -45,6 +45,35 @@ def test_bench_single_process_cpu():
     _check(recs[0], 1)
 
 
+FULL_ONLY = {"test_acc_after", "local_train_ms"}
+
+
+def test_bench_plain_vs_full_and_dump_outputs(tmp_path):
+    """A plain run reports only the timed rounds; ``--full`` adds the evaluation and the per-phase calibration.
+    ``--dump-outputs`` writes the last timed round's global model and metrics, which depend on the arguments alone:
+    the plain and the ``--full`` run (whose extra rounds come after the dump) write the same arrays."""
+    import numpy as np
+    bench = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + SMALL
+    plain = _run(bench + ["--dump-outputs", str(tmp_path / "a")])
+    full = _run(bench + ["--full", "--dump-outputs", str(tmp_path / "b")])
+    assert len(plain) == 1 and len(full) == 1
+    _check(plain[0], 1)
+    _check(full[0], 1)
+    assert not (FULL_ONLY & plain[0].keys()) and FULL_ONLY <= full[0].keys()
+    assert plain[0].keys() - {"value", "ms_per_step"} <= full[0].keys()
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) == ["global_params.npy", "round_metrics.npy"]
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all()
+        assert a.dtype == b.dtype and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    m = np.load(tmp_path / "a" / "round_metrics.npy")      # [loss sum, correct, samples, local steps, saturated]
+    assert m[2] == 4 * 8 and m[3] == 4 and m[4] == 0       # SMALL: 4 clients x 1 local step x batch 8
+
+
 def test_bench_two_ranks_gloo():
     recs = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                  "--master-addr", "127.0.0.1", "--master-port", "29627", os.path.join(ROOT, "bench.py"),

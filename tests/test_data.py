@@ -1,8 +1,10 @@
-"""Data layer: IDX I/O, preprocessing split sizes, partitioner parity with the reference, features."""
-import importlib.util
+"""Data layer: IDX I/O, preprocessing split sizes, partitioner parity with the reference, features.
+
+The reference's side of the parity checks is stored under ``tests/golden/`` (see its README): the MNIST label files
+it ships, and the partitions its ``create_iid_partition`` / ``create_non_iid_partition`` returned for the inputs and
+seeds used below."""
 import os
 import random
-import sys
 
 import numpy as np
 import pytest
@@ -13,21 +15,19 @@ from qfedx_amd.data import (create_iid_partition, create_non_iid_partition, down
                             write_idx_images, write_idx_labels, write_synthetic_mnist, StandardPCA, partition,
                             class_distribution, load_iris_federated, load_synthetic_federated)
 
-REF = "/root/reference"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+RAW_LABELS = os.path.join(GOLDEN, "mnist_raw")
 
 
-def _load_ref(mod_path, name):
-    """Import a reference module read-only (behaviour parity tests; nothing is copied)."""
-    if not os.path.exists(mod_path):
-        pytest.skip("reference not mounted")
-    sys.dont_write_bytecode = True
-    d = os.path.dirname(mod_path)
-    if d not in sys.path:
-        sys.path.insert(0, d)
-    spec = importlib.util.spec_from_file_location(name, mod_path)
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+@pytest.fixture(scope="module")
+def ref_partitions():
+    """Recorded outputs of the reference partitioners: ``<case>_x<i>`` / ``<case>_y<i>`` per client."""
+    with np.load(os.path.join(GOLDEN, "reference_partitions.npz")) as z:
+        return {k: z[k] for k in z.files}
+
+
+def _recorded(rec, case):
+    return [(rec[f"{case}_x{i}"], rec[f"{case}_y{i}"]) for i in range(int(rec[f"{case}_n"]))]
 
 
 def test_idx_roundtrip(tmp_path):
@@ -41,19 +41,17 @@ def test_idx_roundtrip(tmp_path):
 
 
 def test_reference_label_files_parse():
-    p = os.path.join(REF, "dataset/raw/train-labels.idx1-ubyte")
-    if not os.path.exists(p):
-        pytest.skip("reference labels absent")
-    y = read_idx_labels(p, strict=True)
+    y = read_idx_labels(os.path.join(RAW_LABELS, "train-labels.idx1-ubyte"), strict=True)
     assert y.shape == (60000,) and y.max() == 9
+    y = read_idx_labels(os.path.join(RAW_LABELS, "t10k-labels.idx1-ubyte"), strict=True)
+    assert y.shape == (10000,) and y.max() == 9
 
 
 @pytest.fixture(scope="module")
 def synth_raw(tmp_path_factory):
     d = tmp_path_factory.mktemp("mnist")
-    src = os.path.join(REF, "dataset/raw") if os.path.isdir(os.path.join(REF, "dataset/raw")) else None
-    write_synthetic_mnist(str(d / "raw"), src, seed=0)
-    return d, src is not None
+    write_synthetic_mnist(str(d / "raw"), RAW_LABELS, seed=0)
+    return d, True
 
 
 def test_preprocess_split_sizes_match_reference(synth_raw):
@@ -79,37 +77,34 @@ def test_preprocess_missing_files_returns_none(tmp_path, capsys):
     assert preprocess_mnist(str(tmp_path / "nope"), str(tmp_path / "p"), plots=False) is None
 
 
-def test_iid_partition_parity_with_reference():
-    ref = _load_ref(os.path.join(REF, "src/CFed/Preprocess.py"), "ref_preprocess")
+def test_iid_partition_parity_with_reference(ref_partitions):
     X = np.arange(103 * 2).reshape(103, 2)
     y = (np.arange(103) % 3).astype(np.uint8)
-    random.seed(7)
-    a = ref.create_iid_partition(X, y, 4)
+    a = _recorded(ref_partitions, "iid")        # the reference's partition of (X, y, 4) after random.seed(7)
     random.seed(7)
     b = create_iid_partition(X, y, 4)
+    assert len(a) == len(b) == 4
     for (xa, ya), (xb, yb) in zip(a, b):
         assert np.array_equal(xa, xb) and np.array_equal(ya, yb)
     assert [len(p[1]) for p in b] == [25, 25, 25, 28]   # remainder to the last client
 
 
-def test_non_iid_partition_parity_and_label_fix():
-    ref = _load_ref(os.path.join(REF, "src/CFed/Preprocess.py"), "ref_preprocess")
+def test_non_iid_partition_parity_and_label_fix(ref_partitions):
     X = np.arange(300).reshape(300, 1)
     y = (np.arange(300) % 3).astype(np.uint8)
-    random.seed(3)
-    np.random.seed(3)
-    a = ref.create_non_iid_partition(X, y, 5, 0.5)
+    # the reference's partition of (X, y, 5, 0.5) after random.seed(3), np.random.seed(3)
+    a = _recorded(ref_partitions, "noniid")
     random.seed(3)
     np.random.seed(3)
     b = create_non_iid_partition(X, y, 5, 0.5)
+    assert len(a) == len(b) == 5
     for (xa, ya), (xb, yb) in zip(a, b):   # identical for contiguous labels {0..C-1}
         assert np.array_equal(xa, xb) and np.array_equal(ya, yb)
     # digits (3, 5) - the reference keeps nothing, the fixed version keeps all
     y35 = np.where(np.arange(200) % 2 == 0, 3, 5).astype(np.uint8)
     X35 = np.arange(200).reshape(200, 1)
-    random.seed(1)
-    np.random.seed(1)
-    assert sum(len(p[1]) for p in ref.create_non_iid_partition(X35, y35, 4)) == 0
+    # (its client sizes for (X35, y35, 4) after random.seed(1), np.random.seed(1) are recorded)
+    assert ref_partitions["noniid35_sizes"].shape == (4,) and ref_partitions["noniid35_sizes"].sum() == 0
     random.seed(1)
     np.random.seed(1)
     assert sum(len(p[1]) for p in create_non_iid_partition(X35, y35, 4)) == 200

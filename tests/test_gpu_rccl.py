@@ -53,9 +53,9 @@ def test_single_rank_rccl_round_matches_no_group(kw):
 
 
 def test_bench_rccl_single_rank():
-    """bench.py with --dist-backend nccl at one GPU: the round's all-reduce, barrier and max-over-ranks go
+    """bench.py --full with --dist-backend nccl at one GPU: the round's all-reduce, barrier and max-over-ranks go
     through RCCL; the JSON line reports it, with the per-phase times and the precision fields."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dist-backend", "nccl", "--qubits", "12",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--dist-backend", "nccl", "--qubits", "12",
            "--clients", "8", "--batch", "8", "--steps", "3", "--warmup", "2"]
     r = subprocess.run(cmd, cwd="/tmp", capture_output=True, text=True, timeout=300,
                        env=dict(os.environ, MASTER_ADDR="127.0.0.1"))
