@@ -126,8 +126,7 @@ class RuntimeConfig:
     tracking_dir: str = ""              # MLflow file-store root (e.g. ./mlruns); "" = off
     experiment: str = ""                # tracking experiment name ("" = config name)
     log_every: int = 5
-    overlap_comm: bool = True
-    use_graphs: bool = True            # hipGraph capture of the local round (HIP backend)
+    use_graphs: bool = True            # hipGraph capture of the local round (HIP backend; fl/round_graph.py RoundGraph)
     graph_comm: bool = True            # capture the round's all-reduce + apply into that graph (RCCL / no group)
     # CC4: with more than one rank, round r + 1's theta-independent inputs (setup, minibatch plan, tables, gather +
     # encode) are built while round r's collective is in flight (gloo: async all-reduce).  overlap_comm_device: the

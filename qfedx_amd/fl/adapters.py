@@ -62,7 +62,7 @@ class VQCAdapter:
                                 noise=self.noise, mps_chi=int(getattr(m, "mps_chi", 64)))
         self.trainer = VQCClientTrainer(self.spec, self.engine, cfg.train, device, backend)
         # QR/SVD recompression is data dependent: the MPS round runs eagerly, not as a captured graph
-        self.trainer.graphs = bool(getattr(cfg.runtime, "use_graphs", True)) and sim not in ("mps", "density")
+        self.trainer.graphs = bool(cfg.runtime.use_graphs) and sim not in ("mps", "density")
         self.n_params = self.spec.n_params
         self.eval_batch = 4096
 

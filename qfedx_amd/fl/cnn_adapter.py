@@ -15,7 +15,8 @@ import torch.nn.functional as F
 from ..models import tinycnn as tc
 from .optim import BatchedOptimizer
 from ..utils.device import PackedUpload
-from .trainer import UPFRONT_GATHER_BYTES, BatchPlan, ShardStore
+from .round_graph import RoundCtx
+from .trainer import UPFRONT_GATHER_BYTES, ShardStore, round_tables
 
 
 class CNNClientTrainer:
@@ -24,6 +25,7 @@ class CNNClientTrainer:
         self.cfg = train_cfg
         self.device = torch.device(device)
         self.backend = backend
+        self.cc4 = False                # (set by the runner; the CNN round has no side-stream form)
         self._hip = None
         if backend == "hip":
             from ..ops.cnn_hip import HipTinyCNN
@@ -45,30 +47,17 @@ class CNNClientTrainer:
     def run_round(self, store: ShardStore, local_idx: list, theta_g: torch.Tensor, round_num: int,
                   epilogue=None, extra=None, post=None) -> dict:
         """Same contract as ``VQCClientTrainer.run_round`` (per-step [S,K] loss/correct round buffers, optional
-        ``extra`` per-client tables and device ``epilogue``, here run eagerly; ``post`` is left to the caller)."""
+        ``extra`` per-client tables and device ``epilogue``, here run eagerly (``ctx.eager``); ``post`` is left to
+        the caller)."""
         cfg = self.cfg
         K = len(local_idx)
         P = theta_g.numel()
-        if K == 0:
-            z = torch.zeros(0, 0, device=self.device)
-            return {"params": torch.zeros(0, P, device=self.device), "loss": z, "correct": z, "nvalid": z, "act": z,
-                    "lid": torch.zeros(0, dtype=torch.int64, device=self.device), "samples": 0.0, "steps": 0,
-                    "client_ids": [], "n_samples": torch.zeros(0, dtype=torch.float64)}
-        li = torch.tensor(local_idx, dtype=torch.int64)
         cids = [store.client_ids[i] for i in local_idx]
-        plan = BatchPlan(store.counts[li], cids, cfg.batch_size, round_num, cfg.seed, cfg.local_epochs,
-                         cfg.local_steps)
-        nvalid = (plan.wts > 0).sum(-1).float() * plan.active
-        if plan.idx.numel() and int(plan.idx.max()) >= max(1, store.nmax):
-            raise RuntimeError("minibatch plan indexes past the client store")
-        tabs = {"lid": li, "idx": plan.idx, "wts": plan.wts, "act": plan.active, "nvalid": nvalid,
-                "w": store.counts[li].to(torch.float64)}
-        if self._hip is not None:   # dropout Philox keys ride with the round's tables; the head draws the masks
-            tabs["dkeys"] = tc.dropout_keys(cids, cfg.seed, round_num)
-        for name, t in (extra or {}).items():
-            if name in tabs or t.shape[0] != K:
-                raise ValueError(f"extra table {name!r} must be a new per-client [K, ...] table")
-            tabs[name] = t
+        # dropout Philox keys ride with the round's tables; the head draws the masks
+        dkeys = {"dkeys": tc.dropout_keys(cids, cfg.seed, round_num)} if (self._hip is not None and K) else None
+        plan, tabs, common = round_tables(store, local_idx, cfg, round_num, dkeys, extra, P=P, device=self.device)
+        if plan is None:
+            return common
         dv = PackedUpload(tabs).to_device(self.device)
         params = torch.empty(K, P, dtype=torch.float32, device=self.device)
         opt = BatchedOptimizer(cfg.optimizer if cfg.optimizer != "spsa" else "sgd", (K, P), self.device,
@@ -125,10 +114,10 @@ class CNNClientTrainer:
                 loss_all[s].copy_(res["loss"])
                 correct_all[s].copy_(res["correct"])
         if epilogue is not None:
-            epilogue(params, dict(dv, loss=loss_all, correct=correct_all, eager=True), theta_g.to(self.device).float())
+            epilogue.reduce(params, dict(dv, loss=loss_all, correct=correct_all), theta_g.to(self.device).float(),
+                            RoundCtx(eager=True))
         return {"params": params, "loss": loss_all, "correct": correct_all, "nvalid": dv["nvalid"], "act": dv["act"],
-                "lid": dv["lid"], "weights": dv["w"], "samples": float(nvalid.sum()), "steps": int(sum(plan.steps_per_client)),
-                "client_ids": cids, "n_samples": store.counts[li].to(torch.float64)}
+                "lid": dv["lid"], "weights": dv["w"], **common}
 
 
 class TinyCNNAdapter:

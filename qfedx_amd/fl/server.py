@@ -35,12 +35,18 @@ from ..utils.logging import MetricsWriter, get_logger
 from ..utils.seeding import generator, np_rng
 from ..utils.timing import PhaseTimer
 from .aggregator import EXACT_SCALE, Aggregator
+from .epilogue import DeviceRoundEpilogue
 from .trainer import ShardStore
 
-# single-rank rounds apply the update inside the FedAvg reduce launch (FusedApply: every block arrives on one counter)
-# up to this many buffer entries: past it the arrivals, one same-address atomic per 64-parameter block, cost more
-# than the round_apply launch they save (CFed TinyCNN, 128 clients: +9 us per round, profiles/r4_round_structure_ab.txt)
-FUSED_APPLY_MAX = 4096
+
+def cc4_modes(runtime, distributed: bool) -> tuple:
+    """CC4, ``(host_prefetch, device_side_stream)``: round r + 1's theta-independent work overlaps round r's
+    collective - on the host (async all-reduce + ``_prefetch``), and on the graphed HIP round's side stream (opt-in:
+    see ``RuntimeConfig.overlap_comm_device``).  With more than one rank; QFEDX_CC4=0 / 1 overrides both."""
+    env = os.environ.get("QFEDX_CC4")
+    if env is not None:
+        return env == "1", env == "1"
+    return distributed and bool(runtime.overlap_comm), distributed and bool(runtime.overlap_comm_device)
 
 
 def sample_participants(num_clients: int, fraction: float, seed: int, round_num: int,
@@ -123,7 +129,7 @@ class FederatedRunner:
         self.y_test = yt[sl[0]: sl[-1] + 1].to(device) if sl else yt[:0].to(device)
         self.metrics = MetricsWriter(cfg.runtime.metrics_path, world.rank, cfg.to_dict(), cfg.runtime.tracking_dir,
                                      cfg.runtime.experiment or cfg.name)
-        self.timer = PhaseTimer(device, every=int(getattr(cfg.runtime, "timer_every", 0) or
+        self.timer = PhaseTimer(device, every=int(cfg.runtime.timer_every or
                                                   (16 if torch.device(device).type == "cuda" else 1)))
         self.start_round = 0
         self.history: list[dict] = []
@@ -138,21 +144,21 @@ class FederatedRunner:
         # CC6: per-client update norms in the round all-reduce.  Opt-in NON-PRIVATE diagnostic: the raw pre-clip norms
         # (and the clip fraction / quantiles logged from them) are computed from private data without noise and are
         # not charged to the accountant, so a run that logs them is outside the epsilon it reports
-        self.n_norm_slots = (self.num_clients if (p.dp and not p.secure_agg and
-                                                  getattr(cfg.runtime, "log_client_norms", False)) else 0)
+        self.n_norm_slots = self.num_clients if (p.dp and not p.secure_agg and cfg.runtime.log_client_norms) else 0
         # CC2: the round's collective captured into the round hipGraph - decided ONCE, agreed by every rank (each
         # rank captures and replays one all-reduce, compared bitwise with an eager one; fl/trainer.py keeps a per-shape
         # eager fallback that preserves the collective order)
-        want = (bool(getattr(cfg.runtime, "graph_comm", True)) and backend == "hip" and self.server_opt is None
+        want = (bool(cfg.runtime.graph_comm) and backend == "hip" and self.server_opt is None
                 and torch.device(device).type == "cuda" and (not world.distributed or world.backend == "nccl"))
         self.graph_comm = agree_graph_comm(world, want)
-        cc4_env = os.environ.get("QFEDX_CC4")
-        self.cc4 = (cc4_env == "1") or (cc4_env is None and world.distributed and
-                                        bool(getattr(cfg.runtime, "overlap_comm", True)))
-        # the graphed HIP round's side-stream upload + gather (opt-in: see RuntimeConfig.overlap_comm_device)
-        adapter.trainer.cc4 = (cc4_env == "1") or (cc4_env is None and world.distributed and
-                                                   bool(getattr(cfg.runtime, "overlap_comm_device", False)))
+        self.cc4, adapter.trainer.cc4 = cc4_modes(cfg.runtime, world.distributed)
         self.graph_comm_mode = ("captured" if self.graph_comm else "eager") if backend == "hip" else "none"
+        # CC4 prefetch of the next round (round, setup, RoundPrefetch), and how many were built
+        self._pre = None
+        self.prefetches = 0
+        self._counts_dev = self.store.counts.to(torch.float64).to(device)
+        # the device round epilogue (HIP, no server optimizer): FedAvg reduce, collective and apply on the device
+        self.epilogue = DeviceRoundEpilogue(self) if backend == "hip" and self.server_opt is None else None
 
     # ------------------------------------------------------------------ eval
     @torch.no_grad()
@@ -257,7 +263,7 @@ class FederatedRunner:
         st = self._round_setup(r)
         pre = self.adapter.trainer.prepare_round(self.store, st["local_alive"], r)
         self._pre = (r, st, pre)
-        self.prefetches = getattr(self, "prefetches", 0) + 1
+        self.prefetches += 1
 
     def run_round(self, r: int, sync: bool = True) -> dict:
         """One federated round.  With ``sync=False`` nothing reads device memory back: the round is
@@ -266,7 +272,7 @@ class FederatedRunner:
         t = self.cfg.train
         p = self.cfg.privacy
         self.timer.step(r)
-        pre_r = self.__dict__.pop("_pre", None)
+        pre_r, self._pre = self._pre, None
         pre = None
         if pre_r is not None and pre_r[0] == r:
             st, pre = pre_r[1], pre_r[2]
@@ -282,114 +288,18 @@ class FederatedRunner:
         # (public: every rank knows the participant set and the dropouts), so the SecAgg sum carries exactly sigma C
         dp_mode = getattr(p, "noise_mode", "local")
         dp_scale = noise_scale(dp_mode, len(participants) - len(dropped)) if (p.dp and dp_mode != "local") else None
-        fast = self.backend == "hip" and self.server_opt is None
+        epi = self.epilogue
+        fast = epi is not None
         trainer = self.adapter.trainer
         if fast:
-            # round epilogue on the device, run by the trainer right after the local steps (captured into the
-            # round's hipGraph): the fused local reduce writes the head of the all-reduce buffer and the last
-            # block of the same launch appends the fixed-point metrics.  Round-dependent inputs (DP noise keys,
-            # uniform FedAvg weights) travel as per-client tables with the round's upload, never as kernel
-            # arguments.
-            if getattr(self, "_round_buf", None) is None:
-                self._round_buf = torch.zeros(P + 6 + self.n_norm_slots, dtype=torch.int64, device=dev)
-                # FusedApply arrival counter (self-resetting); allocated here, eagerly: created inside the round
-                # graph's capture, its zero fill would become a node replayed every round
-                self._apply_cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-            buf = self._round_buf
-            extra = {}
-            if p.dp and ids:
-                from ..ops.fedavg_hip import dp_noise_keys
-                extra["dpkeys"] = dp_noise_keys(ids, r, self.noise_seed)
-            if t.weighting == "uniform":
-                extra["fw"] = torch.ones(len(ids), dtype=torch.float64)
-            if dp_scale is not None and ids:
-                extra["dpscale"] = torch.full((len(ids),), dp_scale, dtype=torch.float32)
-            if p.secure_agg and ids:
-                # SecAgg on the device: every local client's pair-seed keys and mask signs for this round ride with
-                # the round's tables; the fused reduce masks each client's ring element (K18), so the round stays
-                # one graph launch
-                extra["sa_seed"], extra["sa_sign"] = self.secagg.round_tables(ids, participants, dropped,
-                                                                              self.num_clients, r)
-                extra["sa_round"] = torch.full((len(ids),), r, dtype=torch.int32)
-            if self.n_norm_slots and ids:
-                extra["cid"] = torch.tensor(ids, dtype=torch.int32)
-            agg = self.aggregator
-            NN = self.n_norm_slots
-            if getattr(self, "_round_outs", None) is None:     # [metrics | sat | wsum | norms], one per graph variant
-                self._round_outs = [torch.zeros(6 + NN, dtype=torch.float64, device=dev) for _ in range(2)]
-                self._out_writes = [0, 0]
-                self._flip = 0
-            ring = (p.secagg_bits, p.secagg_scale) if p.secure_agg else (0, 1.0)
-            world, params_g, outs = self.world, self.params, self._round_outs
-
-            fused = self.__dict__.setdefault("_apply_fused", {})
-
-            def post(v):
-                # ONE collective per round (CC2+CC3), then finalize + apply in place; captured into the round
-                # graph (variant v writes metrics buffer v) when the collective allows it.  A single-rank round whose
-                # epilogue already applied (variant v, in the same capture) has nothing left to do.
-                if fused.pop("variant", None) == v:
-                    return
-                all_reduce_(buf, world)
-                from ..ops._ext import ext
-                ext().round_apply(buf, P, params_g, 1.0, outs[v], *ring, NN)
-
-            def apply_variant(tabs, theta):
-                """The metrics buffer variant whose post() the single-rank apply may fold into (None: no fold)."""
-                v = tabs.get("variant", self._flip if tabs.get("eager") else None)
-                if (v is not None and not world.distributed and P + 6 + NN <= FUSED_APPLY_MAX
-                        and os.environ.get("QFEDX_FUSED_APPLY", "1") != "0"
-                        and theta.data_ptr() == params_g.data_ptr()):
-                    return v
-                return None
-
-            def fused_tail(tabs, theta):
-                # plain FedAvg (no DP noise / clipping, no SecAgg masks) folded into the MFMA engine's fused Adam
-                # epilogue of the last local step (hea_step.hip, QfxFedTail): same fixed-point terms, int64 atomics
-                # into the zeroed buffer head, metrics packed and (single rank) the round applied by the last client
-                if p.dp or p.secure_agg or NN or agg.backend != "hip" or \
-                        os.environ.get("QFEDX_FED_TAIL", "1") == "0":
-                    return None
-                if getattr(agg, "_mask_u8", None) is None:
-                    agg._mask_u8 = agg.angle_mask.to(torch.uint8).contiguous()
-                if getattr(self, "_tail_cnt", None) is None:
-                    self._tail_cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-                fed = [buf, theta, agg._mask_u8, tabs.get("fw", tabs["w"]), tabs["loss"].reshape(-1),
-                       tabs["correct"].reshape(-1), tabs["nvalid"].reshape(-1), tabs["act"].reshape(-1),
-                       self._tail_cnt]
-                v = apply_variant(tabs, theta)
-                if v is not None:
-                    fed += [params_g, outs[v]]
-                return {"fed": fed, "wrap": bool(agg.wrap), "n_norms": NN, "zero": buf[: P + 1]}
-
-            def epilogue(params_k, tabs, theta):
-                # one launch: the fused reduce writes the buffer head, its last block packs the metrics.  Single
-                # rank, with post(v) known to follow (captured right behind it: tabs["variant"] = v; eager: the
-                # variant post will take) the same launch also applies the round (no collective in between), one
-                # launch fewer per round.  tabs["fed_done"]: the engine already ran all of it (fused_tail).
-                sa = (tabs["sa_seed"], tabs["sa_sign"], tabs["sa_round"]) if "sa_seed" in tabs else None
-                v = apply_variant(tabs, theta)
-                apply = None
-                fused.pop("variant", None)
-                if tabs.get("fed_done"):
-                    if v is not None:
-                        fused["variant"] = v
-                    return
-                if v is not None:
-                    apply = (params_g, outs[v], self._apply_cnt, *ring, NN)
-                    fused["variant"] = v
-                agg.local_reduce(params_k, theta, tabs.get("fw", tabs["w"]), r, ids, out=buf[: P + 1],
-                                 keys=tabs.get("dpkeys"), secagg_tabs=sa, norm_cid=tabs.get("cid"),
-                                 pack=(buf, tabs["loss"].reshape(-1), tabs["correct"].reshape(-1),
-                                       tabs["nvalid"].reshape(-1), tabs["act"].reshape(-1)), apply=apply,
-                                 dp_scale=tabs.get("dpscale"))
-            epilogue.fused_tail = fused_tail
-            graph_comm = self.graph_comm
+            # the round epilogue on the device (fl/epilogue.py), run by the trainer right after the local steps and
+            # captured with them into the round's hipGraph; post (collective + apply) too when the ranks agreed on it
+            extra = epi.begin_round(r, ids, self.params, participants, dropped, dp_scale)
             with self.timer.phase("local_train"):
-                res = trainer.run_round(self.store, local_alive, self.params, r, epilogue=epilogue,
-                                        extra=extra or None, post=post if graph_comm else None)
+                res = trainer.run_round(self.store, local_alive, self.params, r, epilogue=epi, extra=extra or None,
+                                        post=epi.post if self.graph_comm else None)
             if not local_alive:
-                buf.zero_()
+                epi.buf.zero_()
         else:
             with self.timer.phase("local_train"):
                 res = trainer.run_round(self.store, local_alive, self.params, r,
@@ -400,8 +310,6 @@ class FederatedRunner:
                 elif "weights" in res:            # uploaded with the round's tables (no gather launch)
                     w = res["weights"]
                 else:
-                    if getattr(self, "_counts_dev", None) is None:
-                        self._counts_dev = self.store.counts.to(torch.float64).to(dev)
                     w = self._counts_dev[res["lid"]]
                 if local_alive:
                     contrib = self.aggregator.local_reduce(res["params"], self.params, w, r, ids,
@@ -429,14 +337,13 @@ class FederatedRunner:
                 if res.get("post_done"):
                     v = res["post_variant"]
                 else:
-                    v = self._flip
-                    self._flip ^= 1
-                    post(v)
-                self._out_writes[v] += 1
-                comm_bytes = self._round_buf.numel() * 8
-                out = self._round_outs[v]
+                    v = epi.take_variant()
+                    epi.post(v)
+                epi.out_writes[v] += 1
+                comm_bytes = epi.buf.numel() * 8
+                out = epi.outs[v]
                 metrics = out[:5]                                     # + saturated fixed-point terms
-                norms = out[6:6 + NN] if NN else None
+                norms = out[6:6 + epi.NN] if epi.NN else None
             elif self.server_opt is not None:
                 # server optimizer (CC5): small all-reduce of [weight | metrics]; the update sums are
                 # reduce-scattered inside the sharded step and the new params all-gathered
@@ -479,7 +386,7 @@ class FederatedRunner:
             self.accountant.step(q, p.noise_multiplier, 1)
         rec = {"round": r + 1, "participants": len(participants), "dropped": len(dropped), "secagg_aborted": sa_abort,
                "_metrics": metrics, "_t0": t0,
-               "_out_stamp": (v, self._out_writes[v]) if fast else None,
+               "_out_stamp": (v, self.epilogue.out_writes[v]) if fast else None,
                "_norms": (norms, [c for c in participants if c not in dropped_set]) if norms is not None else None,
                "comm_bytes_per_rank": int(comm_bytes),
                "upload_bytes": int(len(participants) - len(dropped)) * (self.P + 1) * 4}
@@ -497,7 +404,7 @@ class FederatedRunner:
         if "_metrics" not in rec:
             return rec
         stamp = rec.pop("_out_stamp", None)
-        if stamp is not None and self._out_writes[stamp[0]] != stamp[1]:
+        if stamp is not None and self.epilogue.out_writes[stamp[0]] != stamp[1]:
             raise RuntimeError(f"round {rec['round']}: its metrics buffer was reused by a later round; resolve "
                                "records (resolve_record) within two rounds")
         m = rec.pop("_metrics").double().cpu().tolist()

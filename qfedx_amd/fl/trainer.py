@@ -11,18 +11,15 @@ fixes the step count for every client (benchmarks).
 """
 from __future__ import annotations
 
-import math
-import os
-import time
-
 import numpy as np
 from typing import Optional
 
 import torch
 
-from ..utils.device import PackedUpload, h2d
+from ..utils.device import PackedUpload
 from ..utils.seeding import _philox4x32_np, philox4x32, philox_key
 from .optim import BatchedOptimizer
+from .round_graph import WAIT_S, GraphLRU, RoundCtx, RoundGraph, graph_key     # noqa: F401  (WAIT_S: read by bench.py)
 
 # The round prologue gathers every step's inputs up front below this buffer size.  The buffer lives in the round
 # graph's private pool and up to _GRAPH_LRU graphs stay cached, so the cap bounds that reserve too (1.5 GiB).
@@ -31,36 +28,8 @@ UPFRONT_GATHER_BYTES = 1 << 28
 # from the pinned buffer): one launch fewer at the 8-client share (9.7 -> 8.1 us); at 2,048 one-row blocks the pinned
 # index reads took 35 us.  Short rows are packed 16 to a block since (64 clients: 128 gather blocks).
 FOLD_UPLOAD_MAX_BLOCKS = 512
-FOLD_UPLOAD = os.environ.get("QFEDX_FOLD_UPLOAD", "1") != "0"     # (A/B knob)
 _GRAPH_LRU = 6
 
-
-
-def _wait_rounds(ent: dict, n: int) -> None:
-    """Block until graph entry ``ent`` has finished the uploads of ``n`` replays (the round's first node, the upload
-    kernel, publishes the count to a coherent pinned word once every block has read its pinned buffer): spins
-    briefly, then yields; the GPU is normally far ahead of this."""
-    if n <= 0:
-        return
-    flag = ent["flag"].view(torch.int64)
-    if int(flag[0]) >= n:
-        return
-    spins, t0, tw = 0, None, time.perf_counter()
-    while int(flag[0]) < n:
-        spins += 1
-        if spins > 64:
-            time.sleep(20e-6)
-            if t0 is None:
-                t0 = time.perf_counter()
-            elif time.perf_counter() - t0 > 5.0:     # never expected: drain the GPU, then the word must be there
-                torch.cuda.synchronize()
-                if int(flag[0]) < n:
-                    raise RuntimeError(f"round signal stuck at {int(flag[0])} < {n}: device writes to the coherent "
-                                       "pinned word are not visible to the host")
-    WAIT_S[0] += time.perf_counter() - tw
-
-
-WAIT_S = [0.0]     # host seconds spent waiting for the GPU in _wait_rounds (bench: host enqueue cost = loop - wait)
 
 class ShardStore:
     """Device-resident padded shards: X [K, Nmax, F], y [K, Nmax], counts [K]."""
@@ -217,22 +186,34 @@ def _native_runtime():
     return _NATIVE[0]
 
 
-def _tail(epilogue, dv, theta, variant=None, eager=False):
-    """The round epilogue's FedAvg as a ``fed_tail`` maker for the last local step (``epilogue.fused_tail``), or None.
-    The returned callable gets ``done = True`` when the engine ran the FedAvg itself (the epilogue then skips it)."""
-    make = getattr(epilogue, "fused_tail", None)
-    if make is None:
-        return None
-
-    def tail(loss_all, correct_all):
-        tabs = dict(dv, loss=loss_all, correct=correct_all)
-        if variant is not None:
-            tabs["variant"] = variant
-        if eager:
-            tabs["eager"] = True
-        return make(tabs, theta)
-    tail.done = False
-    return tail
+def round_tables(store: ShardStore, local_idx: list, cfg, round_num: int, *extras, P: int = 0, device="cpu"):
+    """A round's host side for clients ``store[local_idx]``: ``(plan, tables, common)`` - the keyed minibatch plan,
+    the host tables the round uploads (store slots, minibatch indices, loss weights, step masks, valid samples,
+    FedAvg sample-count weights, then every per-client [K, ...] table of ``extras``) and the host fields every round
+    record carries.  Without clients: ``(None, None, record)``, the whole record of an empty round (``P``,
+    ``device``)."""
+    K = len(local_idx)
+    if K == 0:
+        z = torch.zeros(0, 0, device=device)
+        return None, None, {"params": torch.zeros(0, P, device=device), "loss": z, "correct": z, "nvalid": z,
+                            "act": z, "lid": torch.zeros(0, dtype=torch.int64, device=device), "samples": 0.0,
+                            "steps": 0, "client_ids": [], "n_samples": torch.zeros(0, dtype=torch.float64)}
+    li = torch.tensor(local_idx, dtype=torch.int64)
+    cids = [store.client_ids[i] for i in local_idx]
+    plan = BatchPlan(store.counts[li], cids, cfg.batch_size, round_num, cfg.seed, cfg.local_epochs, cfg.local_steps)
+    nvalid = (plan.wts > 0).sum(-1).float() * plan.active
+    common = {"samples": float(nvalid.sum()), "steps": int(sum(plan.steps_per_client)), "client_ids": cids,
+              "n_samples": store.counts[li].to(torch.float64)}
+    if plan.idx.numel() and int(plan.idx.max()) >= max(1, store.nmax):   # the gather kernel trusts the table
+        raise RuntimeError("minibatch plan indexes past the client store")
+    tabs = {"lid": li, "idx": plan.idx, "wts": plan.wts, "act": plan.active, "nvalid": nvalid,
+            "w": store.counts[li].to(torch.float64)}   # FedAvg sample-count weights
+    for extra in extras:
+        for name, t in (extra or {}).items():
+            if name in tabs or t.shape[0] != K:
+                raise ValueError(f"extra table {name!r} must be a new per-client [K, ...] table")
+            tabs[name] = t
+    return plan, tabs, common
 
 
 class RoundPrefetch:
@@ -255,6 +236,12 @@ class VQCClientTrainer:
         self.cfg = train_cfg
         self.device = torch.device(device)
         self.backend = backend
+        self.graphs = True              # replay HIP rounds as hipGraphs (runtime.use_graphs; see use_graph)
+        self.cc4 = False                # side-stream upload + gather for graphed rounds (set by the runner)
+        self.graph_comm = True          # capture post() into the round graph; cleared by a capture fallback
+        self.capture_fallbacks = 0
+        self.prefetch_hits = 0
+        self._graph_cache = GraphLRU(_GRAPH_LRU)
 
     def encode(self, X: torch.Tensor) -> torch.Tensor:
         return self.spec.encode_features(X)
@@ -271,14 +258,22 @@ class VQCClientTrainer:
         spec = self.spec
         return 2 if spec.amplitude else (1 if spec.feature_scale == "minmax" else 0)
 
-    def _body(self, X, Y, lid, theta, idx_d, wts_d, act_d, steps: int, round_num: int, method: str,
-              traj_keys=None, ro_keys=None, tail=None, batches=None, xy=None):
+    def _round(self, store, dv, theta, steps: int, round_num: int, method: str, epilogue, ctx: RoundCtx, **kw):
+        """The local steps, then the epilogue's reduce on their outputs (capturable)."""
+        out = self._body(store.X, store.y, dv, theta, steps, round_num, method, epilogue=epilogue, ctx=ctx, **kw)
+        if epilogue is not None:
+            epilogue.reduce(out[0], dict(dv, loss=out[1], correct=out[2]), theta, ctx)
+        return out
+
+    def _body(self, X, Y, dv, theta, steps: int, round_num: int, method: str, traj_keys=None, ro_keys=None,
+              epilogue=None, ctx: Optional[RoundCtx] = None, batches=None, xy=None, upload=None):
         """Device work of one round (capturable): local steps of all clients.
 
-        ``X`` [Nc, Nmax, F] / ``Y`` [Nc, Nmax] are the whole device-resident client store and ``lid`` [K]
-        the round's store slots: on HIP each step's minibatch is gathered and angle-encoded straight from
-        the store by one kernel (no per-round copy of the clients' shards), the round starts with one
-        params/optimizer-state init kernel.
+        ``X`` [Nc, Nmax, F] / ``Y`` [Nc, Nmax] are the whole device-resident client store and ``dv`` the round's
+        device tables (``lid`` [K]: the round's store slots): on HIP each step's minibatch is gathered and
+        angle-encoded straight from the store by one kernel (no per-round copy of the clients' shards), the round
+        starts with one params/optimizer-state init kernel.  ``upload``: the round graph's pending host upload
+        (``RoundGraph.upload_job``), done here ahead of every reader of the tables.
 
         Returns (params [K,P], loss [S,K], correct [S,K]): per-step, per-client weighted loss and hit
         counts are written straight into round buffers by the readout kernel (no per-step metric ops);
@@ -288,6 +283,7 @@ class VQCClientTrainer:
         cfg, spec = self.cfg, self.spec
         noise = self.engine.noise
         T = noise.trajectories if (noise is not None and spec.noisy) else 1
+        lid, idx_d, wts_d, act_d = dv["lid"], dv["idx"], dv["wts"], dv["act"]
         K = lid.shape[0]
         P = theta.numel()
         params = torch.empty(K, P, dtype=torch.float32, device=self.device)
@@ -302,18 +298,17 @@ class VQCClientTrainer:
         # and encoded up front (trajectory replicas, T > 1, and rounds whose inputs pass UPFRONT_GATHER_BYTES
         # gather per step)
         upfront = fused and T == 1 and steps * K * BT * X.shape[-1] * 4 <= UPFRONT_GATHER_BYTES
-        # xy: every step's minibatches already gathered into these buffers on the side stream (CC4, _graphed): the
+        # xy: every step's minibatches already gathered into these buffers on the side stream (CC4, RoundGraph): the
         # prologue only sets the client rows (and the first step's fragments); no upload or gather here
         pregathered = xy is not None and upfront
-        # the round graph's host upload (_graphed): folded into the prologue launch while its gather is small (each
+        # the round graph's host upload: folded into the prologue launch while its gather is small (each
         # gather block reads its indices from the pinned buffer itself: csrc/train_kernels.hip UploadJob), else its
         # own copy kernel here, ahead of every reader of the uploaded tables
-        pend = self.__dict__.pop("_pending_upload", None)
-        if pend is not None and not (upfront and idx_d.is_contiguous() and FOLD_UPLOAD
-                                     and self._gather_blocks(steps * K * BT, X.shape[-1]) <= FOLD_UPLOAD_MAX_BLOCKS):
+        if upload is not None and not (upfront and idx_d.is_contiguous() and
+                                       self._gather_blocks(steps * K * BT, X.shape[-1]) <= FOLD_UPLOAD_MAX_BLOCKS):
             from ..ops._ext import ext
-            ext().host_upload(*pend)
-            pend = None
+            ext().host_upload(*upload)
+            upload = None
         if fused:
             from ..ops._ext import ext
             mode = self._gather_mode()
@@ -327,9 +322,10 @@ class VQCClientTrainer:
         else:
             rows = lid[:, None]
         fj = None
-        # ``tail(loss_all, correct_all)``: the round epilogue's FedAvg as a ``fed_tail`` for the last step's engine
-        # call (the MFMA engine folds it into its fused Adam epilogue); ``tail.done`` says the engine ran it
-        ft = tail(loss_all, correct_all) if (tail is not None and fused and method == "adjoint") else None
+        # the round epilogue's FedAvg as a ``fed_tail`` for the last step's engine call (the MFMA engine folds it into
+        # its fused Adam epilogue); ``ctx.fed_done`` tells the epilogue's reduce that the engine ran it
+        make = getattr(epilogue, "fused_tail", None) if (fused and method == "adjoint") else None
+        ft = make(dict(dv, loss=loss_all, correct=correct_all), theta, ctx) if make is not None else None
         if upfront:
             m, v, t = opt.init_state()
             # the MFMA engine's first-step fragments come from theta in the same launch (every row starts as theta);
@@ -340,7 +336,7 @@ class VQCClientTrainer:
                                  float(spec.alpha), xbuf[:0] if pregathered else xbuf, ybuf, frag_job=fj,
                                  frag_bf16=bool(getattr(self.engine.hip, "bf16", False)),
                                  zero=ft["zero"] if ft is not None else None,
-                                 upload=list(pend) if pend is not None else None)
+                                 upload=list(upload) if upload is not None else None)
         else:
             ft = None                                  # (the tail needs the prologue's zeroed buffer head)
             opt.init_round(params, theta.float())
@@ -373,7 +369,7 @@ class VQCClientTrainer:
                                              shared_frags=fj[1] if (fj is not None and s == 0) else None,
                                              fed_tail=ft if s == steps - 1 else None)
             if res.get("fed_done", False):
-                tail.done = True
+                ctx.fed_done = True
             if not res.get("opt_done", False):      # the MFMA engine runs HIP Adam inside its gradient reduction
                 opt.step(params, res["grad"], act_d[s])
         return params, loss_all, correct_all
@@ -383,33 +379,18 @@ class VQCClientTrainer:
         """The theta-INDEPENDENT part of a round (CC4): the keyed minibatch plan, the round's host tables and, on the
         portable path, every step's gathered and encoded minibatch.  The server builds round r + 1's while round r's
         collective is in flight (``all_reduce_async``); on the graphed HIP path the upload and the gather of round
-        r + 1 run on a side stream against round r's graph (``_graphed``, ``cc4``).  ``gather=False``: tables only."""
+        r + 1 run on a side stream against round r's graph (``RoundGraph``, ``cc4``).  ``gather=False``: tables only."""
         cfg = self.cfg
-        K = len(local_idx)
         pre = RoundPrefetch(round_num, list(local_idx))
-        if K == 0:
+        if len(local_idx) == 0:
             return pre
-        li = torch.tensor(local_idx, dtype=torch.int64)
-        cids = [store.client_ids[i] for i in local_idx]
-        plan = BatchPlan(store.counts[li], cids, cfg.batch_size, round_num, cfg.seed,
-                         cfg.local_epochs, cfg.local_steps)
-        nvalid = (plan.wts > 0).sum(-1).float() * plan.active
-        pre.common = {"samples": float(nvalid.sum()), "steps": int(sum(plan.steps_per_client)), "client_ids": cids,
-                      "n_samples": store.counts[li].to(torch.float64)}
-        if plan.idx.numel() and int(plan.idx.max()) >= max(1, store.nmax):   # the gather kernel trusts the table
-            raise RuntimeError("minibatch plan indexes past the client store")
-        tabs = {"lid": li, "idx": plan.idx, "wts": plan.wts, "act": plan.active, "nvalid": nvalid,
-                "w": store.counts[li].to(torch.float64)}   # FedAvg sample-count weights
-        for name, t in (extra or {}).items():
-            if name in tabs or t.shape[0] != K:
-                raise ValueError(f"extra table {name!r} must be a new per-client [K, ...] table")
-            tabs[name] = t
-        pre.plan, pre.tabs, pre.cids = plan, tabs, cids
+        plan, tabs, pre.common = round_tables(store, local_idx, cfg, round_num, extra)
+        pre.plan, pre.tabs, pre.cids = plan, tabs, pre.common["client_ids"]
         pre.method = "spsa" if cfg.optimizer == "spsa" else cfg.grad_method
         fused = self.backend == "hip" and store.X.is_cuda
         if gather and not fused and self.engine.noise is None and not self.spec.amplitude:
             # portable path: every step's minibatch gathered and encoded now (theta-independent)
-            rows = li.to(store.X.device)[:, None]
+            rows = tabs["lid"].to(store.X.device)[:, None]
             pre.batches = []
             for s_ in range(plan.max_steps):
                 bi = plan.idx[s_].to(store.X.device)
@@ -425,34 +406,32 @@ class VQCClientTrainer:
         host scalars ``samples`` / ``steps`` and ``n_samples`` (cpu, for weighting).
 
         ``extra``: more per-client host tables [K, ...] uploaded with the round's tables (e.g. DP noise keys).
-        ``epilogue(params, tables, theta)``: device work run right after the local steps, on the trained
-        params (possibly padded with inactive weight-0 rows), the round's device tables and the global params;
-        on the hipGraph path it is captured into the round graph, so it may only launch device work on static
-        buffers (no host values that change per round).
-        ``post()``: the round's collective + global update (all-reduce of the epilogue's buffer, apply to
+        ``epilogue``: an object with ``reduce(params, tables, theta, ctx)`` - device work run right after the local
+        steps, on the trained params (possibly padded with inactive weight-0 rows), the round's device tables (plus
+        ``loss`` / ``correct``), the global params and a ``RoundCtx`` - and optionally ``fused_tail(tables, theta,
+        ctx)``, which may hand the FedAvg to the engine's last local step (it returns the engine's ``fed_tail`` dict
+        or None; ``ctx.fed_done`` then tells ``reduce``).  On the hipGraph path both are captured into the round
+        graph, so they may only launch device work on static buffers (no host values that change per round).
+        ``post(v)``: the round's collective + global update (all-reduce of the epilogue's buffer, apply to
         ``theta_g`` in place), run after the epilogue: captured into the round graph too when possible (then the
         whole round - host upload, local steps, reduce, all-reduce, apply - is ONE graph launch), else run
         eagerly.  The returned ``post_done`` says it ran (the caller must not run it again).
         ``pre``: this round's ``prepare_round`` result, built ahead while the previous round's collective ran (CC4);
         used when it is for the same round and clients (else the tables are built here)."""
         K = len(local_idx)
-        P = theta_g.numel()
         if K == 0:
-            z = torch.zeros(0, 0, device=self.device)
-            return {"params": torch.zeros(0, P, device=self.device), "loss": z, "correct": z, "nvalid": z, "act": z,
-                    "lid": torch.zeros(0, dtype=torch.int64, device=self.device), "samples": 0.0, "steps": 0,
-                    "client_ids": [], "n_samples": torch.zeros(0, dtype=torch.float64)}
+            return round_tables(store, [], self.cfg, round_num, P=theta_g.numel(), device=self.device)[2]
         if pre is None or pre.round_num != round_num or pre.local_idx != list(local_idx) or pre.plan is None:
             pre = self.prepare_round(store, local_idx, round_num, extra, gather=False)
         else:
-            self.prefetch_hits = getattr(self, "prefetch_hits", 0) + 1
+            self.prefetch_hits += 1
         plan, tabs, cids, common, method = pre.plan, pre.tabs, pre.cids, pre.common, pre.method
         noise = self.engine.noise
         graphed = self.use_graph and method == "adjoint" and noise is None
         if graphed:
             tabs = _pad_clients(tabs, graph_bucket(K, len(store)))
             fit = getattr(self.engine, "fit_tiles", None)
-            if fit is not None and not self.__dict__.get("_graph_cache"):
+            if fit is not None and len(self._graph_cache) == 0:
                 # small per-rank batches: smaller MFMA tiles (decided once, before the first round graph)
                 fit(int(tabs["lid"].shape[0]) * plan.B)
         up = PackedUpload(tabs)
@@ -462,7 +441,7 @@ class VQCClientTrainer:
             ro_keys = noise.client_keys("shots", round_num, cids, self.device)
         post_v = None
         if graphed:
-            params, loss_all, correct_all, dv, post_v = self._graphed(store, up, theta_g, plan, round_num,
+            params, loss_all, correct_all, dv, post_v = self._graphed(store, up, tabs, theta_g, plan, round_num,
                                                                       epilogue, post)
             # padding clients (inactive, weight 0) only fill the captured shape: the FedAvg reduce sees the
             # K real rows; their [S, Kpad] metric columns are all zero
@@ -471,13 +450,10 @@ class VQCClientTrainer:
         else:
             dv = up.to_device(self.device)
             theta = theta_g.to(self.device)
-            tail = _tail(epilogue, dv, theta, eager=True)
-            params, loss_all, correct_all = self._body(store.X, store.y, dv["lid"], theta, dv["idx"],
-                                                       dv["wts"], dv["act"], plan.max_steps, round_num, method,
-                                                       traj_keys, ro_keys, tail=tail, batches=pre.batches)
-            if epilogue is not None:    # eager: ``post`` (if any) runs right after, on the caller's side
-                epilogue(params, dict(dv, loss=loss_all, correct=correct_all, eager=True,
-                                      fed_done=bool(tail and tail.done)), theta)
+            # eager: ``post`` (if any) runs right after, on the caller's side
+            params, loss_all, correct_all = self._round(store, dv, theta, plan.max_steps, round_num, method, epilogue,
+                                                        RoundCtx(eager=True), traj_keys=traj_keys, ro_keys=ro_keys,
+                                                        batches=pre.batches)
         return {"params": params, "loss": loss_all, "correct": correct_all, "nvalid": dv["nvalid"], "act": dv["act"],
                 "lid": dv["lid"], "weights": dv["w"], "post_done": post_v is not None, "post_variant": post_v,
                 **common}
@@ -485,169 +461,51 @@ class VQCClientTrainer:
     # ------------------------------------------------------------------ hipGraph capture
     @property
     def use_graph(self) -> bool:
-        return self.backend == "hip" and self.device.type == "cuda" and getattr(self, "graphs", True)
+        return self.backend == "hip" and self.device.type == "cuda" and self.graphs
 
-    def _graphed(self, store, up, theta_g, plan, round_num, epilogue=None, post=None):
+    def _graphed(self, store, up, tabs, theta_g, plan, round_num, epilogue=None, post=None):
         """Replay the whole round as ONE hipGraph (static shapes: #clients, steps, batch).
 
-        Captured once per SHAPE, not per client set, in two variants that differ only in the pinned host buffer
-        their first node reads the round's packed tables from (client slots, minibatch indices, loss weights, step
-        masks, per-client keys; a copy kernel, or the round prologue itself when its gather is small): round r
-        fills pinned buffer r % 2 - free once round r - 2's
-        replay has finished - and replays variant r % 2, so the host stays a round ahead with no upload launch
-        of its own.  The captured launches gather every step's minibatches from the (static) client store by
-        slot, so client sampling reuses the graph.  The global params are read in place when they are a float32
-        device tensor (the runner updates them in place), otherwise copied into a static buffer.  ``epilogue``
-        (the fused FedAvg reduce + metrics pack) and ``post`` (the collective + in-place apply) are captured
-        after the local steps, so a round is one graph launch; if the collective cannot be captured, ``post``
-        runs eagerly after the replay.  A small LRU bounds the live graphs.
-        """
-        K = up.layout[0][4][0]
-        dev = self.device
-        direct = theta_g.is_cuda and theta_g.dtype == torch.float32 and theta_g.is_contiguous()
+        Captured once per SHAPE (``graph_key``: what a capture freezes, what travels per round), not per client set:
+        the captured launches gather every step's minibatches from the (static) client store by slot, so client
+        sampling reuses the graph.  The round's packed tables reach it through a pinned buffer its first node reads
+        (a copy kernel, or the round prologue itself when its gather is small; ``RoundGraph``).  ``epilogue`` and
+        ``post`` are captured after the local steps, so a round is one graph launch; if the collective cannot be
+        captured, ``post`` runs eagerly after the replay.  A small LRU bounds the live graphs."""
+        K = tabs["lid"].shape[0]
         # CC4 (world_size > 1, or QFEDX_CC4=1): the round's host upload and minibatch gather leave the graph for a side
         # stream, into per-variant table / minibatch buffers, so round r + 1's upload + gather run while round r's
         # graph - its local steps, and its all-reduce + apply at the end - is still on the main stream
-        F = store.X.shape[-1]
-        cc4 = bool(getattr(self, "cc4", False)) and plan.max_steps * K * plan.B * F * 4 <= UPFRONT_GATHER_BYTES
-        key = (K, plan.max_steps, plan.B, store.nmax, store.X.data_ptr(), tuple(l[0] for l in up.layout),
-               theta_g.data_ptr() if direct else None, epilogue is not None, post is not None, cc4)
-        cache = self.__dict__.setdefault("_graph_cache", {})
-        ent = cache.pop(key, None)
-        if ent is None:
-            from ..ops._ext import ext
-            E = ext()
-            packs = [torch.empty(up.nbytes, dtype=torch.uint8, device=dev) for _ in range(2 if cc4 else 1)]
-            dvs = [up.to_device(dev, pk) for pk in packs]
-            pack, dv = packs[0], dvs[0]
-            ent = {"pack": pack, "dv": dv, "theta": theta_g if direct else theta_g.to(dev).float().clone(),
-                   "cc4": cc4, "packs": packs, "dvs": dvs,
-                   "pin": [E.host_alloc(up.nbytes), E.host_alloc(up.nbytes)], "flip": 0,
-                   # upload-completion counter (round count + block arrivals) and its coherent host mirror, both
-                   # written by the graph's first node (the upload kernel's last block)
-                   "ctr": torch.zeros(2, dtype=torch.int64, device=dev), "flag": E.host_alloc(8, True),
-                   "launched": 0}
-            ent["flag"].zero_()
-            if cc4:
-                ent["xy"] = [(torch.empty(plan.max_steps, K, plan.B, F, dtype=torch.float32, device=dev),
-                              torch.empty(plan.max_steps * K * plan.B, dtype=torch.int64, device=dev))
-                             for _ in range(2)]
-                ent["side"] = torch.cuda.Stream(device=dev)
-                ent["ev_g"] = [torch.cuda.Event() for _ in range(2)]
-                ent["ev_c"] = [torch.cuda.Event() for _ in range(2)]
-                ent["c_rec"] = [False, False]
-                ent["pshape"] = torch.empty(K, theta_g.numel(), dtype=torch.float32, device=dev)
-
-            def body(variant=None, bv=0):
-                # ``variant``: set when post(variant) is captured right behind the epilogue (it may fold into it);
-                # ``bv``: the variant whose tables / minibatch buffers the capture reads (CC4: one set per variant)
-                d = dvs[bv] if cc4 else dv
-                tail = _tail(epilogue, d, ent["theta"], variant=variant)
-                out = self._body(store.X, store.y, d["lid"], ent["theta"], d["idx"], d["wts"], d["act"],
-                                 plan.max_steps, round_num, "adjoint", tail=tail,
-                                 xy=ent["xy"][bv] if cc4 else None)
-                if epilogue is not None:
-                    tabs = dict(d, loss=out[1], correct=out[2], fed_done=bool(tail and tail.done))
-                    if variant is not None:
-                        tabs["variant"] = variant
-                    epilogue(out[0], tabs, ent["theta"])
-                return out
-            # the graph owns its workspaces: eager calls (evaluation) can never regrow/free them
-            ent["ws"] = {}
-            cur = torch.cuda.current_stream(dev)
-            with self.engine.hip.private_workspace(ent["ws"]):
-                side = torch.cuda.Stream(device=dev)
-                side.wait_stream(cur)
-                with torch.cuda.stream(side):       # warm-up (no collective / apply): modules loaded, sizes fixed
-                    if cc4:     # gather only, from the device tables to_device filled (no pinned upload, no count)
-                        self._cc4_gather(ent, store, up, 0, wait=False, upload=False)
-                    body()
-                cur.wait_stream(side)
-                ent["graphs"], ent["out"] = [], []
-                ent["post_in_graph"] = post is not None and getattr(self, "graph_comm", True)
-                for v in range(2):
-                    up._fill(ent["pin"][v][: up.nbytes])
-                    g = torch.cuda.CUDAGraph()
-                    try:
-                        # thread-local capture: the RCCL watchdog thread queries its work events at any time, and in
-                        # the global mode such a query during the capture aborted the process (hipErrorStreamCapture-
-                        # Unsupported, seen once in tests/test_gpu_rccl.py)
-                        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                            if not cc4:
-                                self._pending_upload = (ent["pin"][v][: up.nbytes], pack, ent["ctr"], ent["flag"])
-                            out = body(v if ent["post_in_graph"] else None, v)
-                            if ent["post_in_graph"]:
-                                post(v)
-                    except Exception as exc:
-                        self.__dict__.pop("_pending_upload", None)
-                        if not ent["post_in_graph"]:
-                            raise
-                        # the collective refused capture although the ranks agreed it could be captured
-                        # (parallel/dist.py agree_graph_comm): graphs without it, post() runs eagerly right after
-                        # the replay - the same point of this rank's collective sequence, so ranks stay matched
-                        import warnings
-                        warnings.warn(f"round collective capture failed ({exc!r}); running it eagerly on this rank")
-                        self.capture_fallbacks = getattr(self, "capture_fallbacks", 0) + 1
-                        self.graph_comm = False
-                        ent["post_in_graph"] = False
-                        torch.cuda.synchronize(dev)
-                        ent["graphs"], ent["out"] = [], []
-                        for v2 in range(2):
-                            g = torch.cuda.CUDAGraph()
-                            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                                if not cc4:
-                                    self._pending_upload = (ent["pin"][v2][: up.nbytes], pack, ent["ctr"],
-                                                            ent["flag"])
-                                out = body(None, v2)
-                            ent["graphs"].append(g)
-                            ent["out"].append(out)
-                        break
-                    ent["graphs"].append(g)
-                    ent["out"].append(out)
-            while len(cache) >= _GRAPH_LRU:         # LRU: drop the oldest shape
-                old = cache.pop(next(iter(cache)))
-                # the counter only says its uploads are done: drain the device before the graph and its
-                # workspaces are released (rare: more live shapes than the LRU holds)
-                _wait_rounds(old, old["launched"])
-                torch.cuda.current_stream(dev).synchronize()
-        cache[key] = ent                            # most recently used last
-        if not direct:
-            ent["theta"].copy_(theta_g.float())
-        v = ent["flip"]
-        ent["flip"] ^= 1
-        n = ent["launched"]
-        _wait_rounds(ent, n - 1)                    # pinned buffer v: its last reader (replay n - 2) is done
-        up._fill(ent["pin"][v][: up.nbytes])
-        if cc4:
-            # side stream: this round's upload + gather, behind only the graph that last read variant v's buffers
-            # (round r - 2); it runs while round r - 1's graph, collective included, is still on the main stream
-            self._cc4_gather(ent, store, up, v)
-            torch.cuda.current_stream(dev).wait_event(ent["ev_g"][v])
-        ent["graphs"][v].replay()
-        if cc4:
-            ent["ev_c"][v].record(torch.cuda.current_stream(dev))
-            ent["c_rec"][v] = True
-        ent["launched"] = n + 1
-        if post is not None and not ent["post_in_graph"]:
+        cc4 = bool(self.cc4) and plan.max_steps * K * plan.B * store.X.shape[-1] * 4 <= UPFRONT_GATHER_BYTES
+        key = graph_key(store, plan, tabs, theta_g, epilogue, post, cc4)
+        g = self._graph_cache.get(key)
+        if g is None:
+            g = RoundGraph(self, store, up, theta_g, key)
+            g.capture(up, epilogue, post, round_num)
+            self._graph_cache.put(key, g)
+        if key.theta_ptr is None:
+            g.theta.copy_(theta_g.float())
+        v = g.replay(up)
+        if post is not None and not g.post_in_graph:
             post(v)
-        return (*ent["out"][v], ent["dvs"][v] if cc4 else ent["dv"], v if post is not None else None)
+        return (*g.out[v], g.tabs(v), v if post is not None else None)
 
-    def _cc4_gather(self, ent, store, up, v: int, wait: bool = True, upload: bool = True) -> None:
+    def _cc4_gather(self, g: RoundGraph, up, v: int, wait: bool = True, upload: bool = True) -> None:
         """The round's theta-independent device work on the side stream (CC4): the upload of the round's tables from
         pinned buffer v into the variant's device tables and every step's minibatch gather + encode, one prologue
         launch without client rows (csrc/train_kernels.hip: its gather blocks read the indices from the pinned copy,
         its last block posts the upload-completion count).  Ordered after the graph that last read variant v."""
         from ..ops._ext import ext
-        side = ent["side"]
-        if wait and ent["c_rec"][v]:
-            side.wait_event(ent["ev_c"][v])
-        d = ent["dvs"][v]
-        xb, yb = ent["xy"][v]
-        with torch.cuda.stream(side):
-            ext().round_prologue(ent["theta"], ent["pshape"], None, None, None, store.X, store.y, d["lid"],
+        sg, store = g.side, g.store
+        if wait and sg.c_rec[v]:
+            sg.stream.wait_event(sg.ev_c[v])
+        d = g.tabs(v)
+        xb, yb = sg.xy[v]
+        with torch.cuda.stream(sg.stream):
+            ext().round_prologue(g.theta, sg.pshape, None, None, None, store.X, store.y, d["lid"],
                                  d["idx"].contiguous(), self._gather_mode(), float(self.spec.alpha), xb, yb,
-                                 rows=False, upload=[ent["pin"][v][: up.nbytes], ent["packs"][v], ent["ctr"],
-                                                     ent["flag"]] if upload else None)
-            ent["ev_g"][v].record(side)
+                                 rows=False, upload=list(g.upload_job(v, up.nbytes)) if upload else None)
+            sg.ev_g[v].record(sg.stream)
         if not wait:
-            torch.cuda.current_stream(self.device).wait_stream(side)
+            torch.cuda.current_stream(self.device).wait_stream(sg.stream)
+

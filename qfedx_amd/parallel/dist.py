@@ -11,7 +11,7 @@ MPI / Slurm (``ROADMAP.md:39,77-89``).  Design here:
 * ``exact`` mode all-reduces a fixed-point int64 encoding: integer sums are associative, so the
   aggregate is bitwise identical for 1/2/4/8 ranks (SURVEY §7.3 item 10);
 * the round's collective and the in-place apply are captured into the round's hipGraph with the local steps
-  (``fl/trainer.py`` ``_graphed``; RCCL accepts capture), so a round is one graph launch with no host
+  (``fl/round_graph.py`` ``RoundGraph.capture``; RCCL accepts capture), so a round is one graph launch with no host
   round trip between training and aggregation.  Nothing of round r + 1 can overlap the collective: its local
   steps start from the theta the collective produces, and the theta-independent part (the minibatch gather of the
   round prologue) is a few microseconds.  A comm-stream / layer-bucket overlap design was removed in round 3 as

@@ -258,6 +258,80 @@ def test_graph_bucket_and_client_padding():
     assert _pad_clients(tabs, 3) is tabs
 
 
+def test_round_graph_lru_drains_then_evicts_the_oldest():
+    """The cache of captured round shapes: capacity 6, most recently used last; the oldest entry is drained exactly
+    once, while it is still in the cache, and then dropped.  (Stub entries: nothing here touches the device.)"""
+    from qfedx_amd.fl.round_graph import GraphLRU
+    from qfedx_amd.fl.trainer import _GRAPH_LRU
+    assert _GRAPH_LRU == 6
+    lru = GraphLRU(_GRAPH_LRU)
+    drains = []
+
+    class Stub:
+        def __init__(self, key):
+            self.key = key
+
+        def drain(self):
+            drains.append((self.key, self.key in lru))
+
+    assert len(lru) == 0 and lru.get("k0") is None
+    for i in range(7):
+        lru.put(f"k{i}", Stub(f"k{i}"))
+        assert len(lru) == min(i + 1, 6)                  # "empty" only before the first insert
+    assert drains == [("k0", True)]                       # drained once, before it left
+    assert "k0" not in lru and list(lru) == [f"k{i}" for i in range(1, 7)]
+    assert lru.get("k2").key == "k2" and list(lru) == ["k1", "k3", "k4", "k5", "k6", "k2"]
+    assert next(reversed(lru.values())).key == "k2" and lru.get("k0") is None
+    assert drains == [("k0", True)]
+
+
+def test_round_tables_builder_is_what_prepare_round_uses():
+    """The shared builder of a round's host tables (VQC and CNN trainers): the same tables and record fields as
+    ``prepare_round``, ``extra`` tables validated, and the empty round's record."""
+    from qfedx_amd.api import setup
+    from qfedx_amd.data.datasets import build_federated_data
+    from qfedx_amd.fl.adapters import make_adapter
+    from qfedx_amd.fl.trainer import ShardStore, round_tables
+    cfg = small_cfg(num_clients=3, batch_size=4)
+    device, backend, world = setup(cfg)
+    data = build_federated_data(cfg)
+    tr = make_adapter(cfg, device, backend).trainer
+    sizes = [5, 9, 12]
+    store = ShardStore([(X[:n], y[:n]) for (X, y), n in zip(data.clients, sizes)], data.client_ids, device)
+    idx = [0, 1, 2]
+    pre = tr.prepare_round(store, idx, 1, gather=False)
+    plan, tabs, common = round_tables(store, idx, cfg.train, 1)
+    assert list(tabs) == list(pre.tabs) == ["lid", "idx", "wts", "act", "nvalid", "w"]
+    for name, t in tabs.items():
+        assert t.dtype == pre.tabs[name].dtype and torch.equal(t, pre.tabs[name]), name
+    assert torch.equal(plan.idx, pre.plan.idx) and plan.steps_per_client == pre.plan.steps_per_client
+    assert list(common) == list(pre.common) == ["samples", "steps", "client_ids", "n_samples"]
+    assert common["samples"] == pre.common["samples"] == float(sum(sizes)) * cfg.train.local_epochs
+    assert common["steps"] == pre.common["steps"] == sum(-(-n // 4) for n in sizes) * cfg.train.local_epochs
+    assert common["client_ids"] == pre.common["client_ids"] == pre.cids == list(data.client_ids)
+    assert torch.equal(common["n_samples"], pre.common["n_samples"]) and tabs["w"].tolist() == [5.0, 9.0, 12.0]
+    keys = torch.arange(6, dtype=torch.int32).reshape(3, 2)
+    assert torch.equal(round_tables(store, idx, cfg.train, 1, {"a": keys}, {"b": keys + 1})[1]["b"], keys + 1)
+    for bad in ({"dpkeys": keys[:2]}, {"w": torch.ones(3)}):
+        with pytest.raises(ValueError):
+            round_tables(store, idx, cfg.train, 1, bad)
+        with pytest.raises(ValueError):
+            round_tables(store, idx, cfg.train, 1, {"dkeys": keys}, bad)
+    with pytest.raises(ValueError):
+        round_tables(store, idx, cfg.train, 1, {"dkeys": keys}, {"dkeys": keys})
+    P = 7
+    none_plan, none_tabs, rec = round_tables(store, [], cfg.train, 1, P=P, device=device)
+    assert none_plan is None and none_tabs is None
+    assert list(rec) == ["params", "loss", "correct", "nvalid", "act", "lid", "samples", "steps", "client_ids",
+                         "n_samples"]
+    assert rec["params"].shape == (0, P) and all(rec[k].shape == (0, 0) for k in ("loss", "correct", "nvalid", "act"))
+    assert rec["lid"].shape == (0,) and rec["lid"].dtype == torch.int64
+    assert rec["samples"] == 0.0 and rec["steps"] == 0 and rec["client_ids"] == []
+    assert rec["n_samples"].shape == (0,) and rec["n_samples"].dtype == torch.float64
+    empty = tr.run_round(store, [], torch.zeros(P), 1)
+    assert list(empty) == list(rec) and empty["params"].shape == (0, P)
+
+
 def test_trainer_epilogue_and_extra_tables():
     """The trainer runs a device epilogue right after the local steps on the trained params, with the round's
     tables (plus caller-provided per-client ``extra`` tables); the server's fused FedAvg uses this hook."""
@@ -273,11 +347,12 @@ def test_trainer_epilogue_and_extra_tables():
     theta = adapter.init_params(0)
     seen = {}
 
-    def epi(params, tabs, th):
-        seen.update(params=params.clone(), keys=tabs["dpkeys"].clone(), loss=tabs["loss"].clone(), theta=th)
+    class Epi:
+        def reduce(self, params, tabs, th, ctx):
+            seen.update(params=params.clone(), keys=tabs["dpkeys"].clone(), loss=tabs["loss"].clone(), theta=th)
 
     keys = torch.arange(4, dtype=torch.int32).reshape(2, 2)
-    res = adapter.trainer.run_round(store, [0, 2], theta, 0, epilogue=epi, extra={"dpkeys": keys})
+    res = adapter.trainer.run_round(store, [0, 2], theta, 0, epilogue=Epi(), extra={"dpkeys": keys})
     assert torch.equal(seen["params"], res["params"]) and torch.equal(seen["keys"], keys)
     assert torch.equal(seen["loss"], res["loss"]) and torch.equal(seen["theta"], theta)
     with pytest.raises(ValueError):

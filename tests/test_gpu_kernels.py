@@ -416,11 +416,58 @@ def test_padded_inactive_client_rows_mfma(cuda):
     for (pg, lg, cg), (pe, le, ce) in zip(outs[True], outs[False]):
         assert lg.shape[0] >= 3                       # several local steps
         assert torch.equal(pg, pe) and torch.equal(lg, le) and torch.equal(cg, ce)
-    ent = next(reversed(tr._graph_cache.values()))
-    p_pad, loss_pad, corr_pad = ent["out"][0][:3]        # graph variant 0's static outputs
+    g = next(reversed(tr._graph_cache.values()))
+    p_pad, loss_pad, corr_pad = g.out[0][:3]             # graph variant 0's static outputs
     assert p_pad.shape[0] == 4
     assert torch.equal(p_pad[3], theta.float())
     assert not loss_pad[:, 3].any() and not corr_pad[:, 3].any()
+
+
+def test_round_collective_capture_fallback(cuda):
+    """A ``post`` that refuses capture (a host exception inside the capture, like a collective that cannot be
+    captured): the round graph is captured again without it, once and with one warning, ``post`` then runs eagerly
+    after every replay, and the rounds are bitwise the eager rounds."""
+    import warnings
+    from tests.test_fl import small_cfg
+    from qfedx_amd.data.datasets import build_federated_data
+    from qfedx_amd.fl.adapters import make_adapter
+    from qfedx_amd.fl.trainer import ShardStore, graph_bucket
+    dev = torch.device("cuda", 0)
+    cfg = small_cfg(n_qubits=10, n_layers=2, num_clients=4, samples_per_client=16, batch_size=8, device="cuda",
+                    backend="hip")
+    data = build_federated_data(cfg, clients=list(range(4)))
+    ad = make_adapter(cfg, dev, "hip")
+    assert ad.state_dtype == "mfma"
+    store = ShardStore(data.clients, data.client_ids, dev)
+    theta = ad.init_params(cfg.train.seed).to(dev)
+    tr = ad.trainer
+    local = [0, 1, 2]
+    assert graph_bucket(len(local), len(store)) == 4
+    ran = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def post(v):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("this collective cannot be captured")
+        ran.add_(1)
+
+    def rounds(**kw):
+        out = []
+        for r in range(2):                            # the second round replays the first round's graph
+            rec = tr.run_round(store, local, theta, r, **kw)
+            out.append((rec["post_done"], rec["params"][: len(local)].clone(),
+                        rec["loss"][:, : len(local)].clone(), rec["correct"][:, : len(local)].clone()))
+        return out
+
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        graphed = rounds(post=post)
+    assert len([w for w in caught if "collective capture failed" in str(w.message)]) == 1
+    assert tr.capture_fallbacks == 1 and tr.graph_comm is False
+    assert int(ran.item()) == len(graphed)            # post ran eagerly, once per round
+    tr.graphs = False
+    for (done, pg, lg, cg), (_, pe, le, ce) in zip(graphed, rounds()):
+        assert done
+        assert torch.equal(pg, pe) and torch.equal(lg, le) and torch.equal(cg, ce)
 
 
 def test_secagg_sparse_graph_in_fused_reduce_match_host_protocol(cuda):
