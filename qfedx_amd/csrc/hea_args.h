@@ -1,7 +1,16 @@
 // Launch arguments of the MFMA statevector pass kernel (csrc/hea_mfma.hip); shared by the host
 // bindings (csrc/hea_bindings.cpp) so both sides agree on the layout.
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <cstdint>
+#else   // hiprtc (per-plan pass kernels, hea_spec.cpp): no libstdc++; what the shared headers use of it
+typedef unsigned int uint32_t;
+typedef unsigned long long uint64_t;
+typedef unsigned long uintptr_t;
+#ifndef INFINITY
+#define INFINITY __builtin_huge_valf()
+#endif
+#endif
 
 // Rows of the stall-attribution buffer (stamps build): STAMP_WG = 2048 workgroups x up to 16 waves.
 constexpr int HEA_STAMP_ROWS = 2048 * 16;

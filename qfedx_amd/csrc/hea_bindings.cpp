@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "hea_args.h"
+#include "hea_spec.h"
 
 extern "C" {
 int qfx_hea_pass(int adjoint, const HeaPassArgs* args, int n_samples, hipStream_t st);
@@ -68,7 +69,7 @@ void hea_pass(bool adjoint, torch::Tensor ops, torch::Tensor fidx, torch::Tensor
               torch::Tensor psi_out, torch::Tensor lam_in, torch::Tensor lam_out, torch::Tensor xang,
               torch::Tensor params, torch::Tensor frags, torch::Tensor wread, torch::Tensor part,
               torch::Tensor gslab, torch::Tensor dbg, c10::optional<std::vector<torch::Tensor>> readout,
-              int64_t ro_tps) {
+              int64_t ro_tps, int64_t spec) {
   need(geom.size() == 31, "geometry vector must have 31 entries");
   const bool bf16 = geom[27] != 0;
   HeaPassArgs a{};
@@ -158,7 +159,10 @@ void hea_pass(bool adjoint, torch::Tensor ops, torch::Tensor fidx, torch::Tensor
   a.gslab = adjoint ? dp<long long>(gslab, torch::kInt64, "gslab", S * a.slab_tiles * a.n_gradops * 32) : nullptr;
   need(!adjoint || a.slab_tiles >= a.n_tiles, "gradient slab has fewer tiles than the pass");
   need(!a.gen || a.n <= 32, "product-state generation supports <= 32 qubits");
-  if (bf16)
+  // spec >= 0: this pass's per-plan kernel (hea_spec.cpp) instead of the interpreter, same grid / block / arguments
+  if (spec >= 0)
+    check(qfx::hea_spec_launch((int)spec, adjoint ? 1 : 0, bf16, &a, (int)S, cur()), "qfx_hea_spec_launch");
+  else if (bf16)
     check(qfx_hea_pass_bf16(adjoint ? 1 : 0, &a, (int)S, cur()), "qfx_hea_pass_bf16");
   else
     check(qfx_hea_pass(adjoint ? 1 : 0, &a, (int)S, cur()), "qfx_hea_pass");
@@ -301,14 +305,57 @@ void hea_grad_reduce(torch::Tensor gslab, int64_t slab_tiles, int64_t n_gradops,
         "qfx_hea_grad_reduce");
 }
 
+// Per-plan pass kernels (hea_spec.cpp).  cfg = [n, t, c, lo, hi, C, gen, load_lam, store_lam, n_regions, H0..H4,
+// bf16, stamps, gate_lo (-1: default)]; ops / fidx: the pass program's host tensors.
+qfx::HeaSpecDesc spec_desc(bool adjoint, torch::Tensor ops, torch::Tensor fidx, std::vector<int64_t> cfg) {
+  need(cfg.size() == 18, "hea_spec: configuration vector must have 18 entries");
+  need(ops.dim() == 2 && ops.size(1) == 128 && ops.scalar_type() == torch::kInt32 && !ops.is_cuda() && ops.is_contiguous(),
+       "hea_spec: ops must be a contiguous host int32 [nops, 128] tensor");
+  need(fidx.scalar_type() == torch::kInt32 && !fidx.is_cuda() && fidx.is_contiguous() && fidx.numel() == 2 * ops.size(0),
+       "hea_spec: fidx must be a host int32 [nops, 2] tensor");
+  qfx::HeaSpecDesc d;
+  d.adjoint = adjoint;
+  d.n = (int)cfg[0], d.t = (int)cfg[1], d.c = (int)cfg[2], d.lo = (int)cfg[3], d.hi = (int)cfg[4], d.ncls = (int)cfg[5];
+  d.gen = cfg[6] != 0, d.load_lam = cfg[7] != 0, d.store_lam = cfg[8] != 0, d.n_regions = (int)cfg[9];
+  for (int b = 0; b < 5; ++b) d.hrow[b] = (int)cfg[10 + b];
+  d.bf16 = cfg[15] != 0, d.stamps = cfg[16] != 0, d.gate_lo = (int)cfg[17];
+  need(d.n >= 8 && d.n <= 30 && d.t >= 8 && d.t <= 14 && d.t <= d.n && d.c >= 2 && d.c <= d.lo && d.lo <= d.hi &&
+       d.hi <= d.n && d.c + d.hi - d.lo == d.t && d.ncls >= 1 && d.ncls <= 8, "hea_spec: bad geometry");
+  for (int b = 0; b < 5; ++b) need(d.hrow[b] >= 0 && d.hrow[b] < (1 << (d.t - 5)), "hea_spec: swizzle row past the tile bits");
+  d.ops.assign(ops.data_ptr<int>(), ops.data_ptr<int>() + ops.numel());
+  d.fidx.assign(fidx.data_ptr<int>(), fidx.data_ptr<int>() + fidx.numel());
+  return d;
+}
+
 }  // namespace
 
 void register_hea(pybind11::module& m) {
+  m.def("hea_spec_source", [](bool adjoint, torch::Tensor ops, torch::Tensor fidx, std::vector<int64_t> cfg) {
+    return qfx::hea_spec_source(spec_desc(adjoint, ops, fidx, cfg));
+  });
+  m.def("hea_spec_key", [](bool adjoint, torch::Tensor ops, torch::Tensor fidx, std::vector<int64_t> cfg,
+                           std::string include_dir, std::string arch) {
+    return qfx::hea_spec_key(spec_desc(adjoint, ops, fidx, cfg), include_dir, arch);
+  });
+  // generate + hiprtc-compile (or load cached) one pass's kernel -> (handle, cache key); needs no GPU
+  m.def("hea_spec_prepare", [](bool adjoint, torch::Tensor ops, torch::Tensor fidx, std::vector<int64_t> cfg,
+                               std::string cache_dir, std::string include_dir, std::string arch) {
+    std::string key;
+    const int h = qfx::hea_spec_prepare(spec_desc(adjoint, ops, fidx, cfg), cache_dir, include_dir, arch, &key);
+    return pybind11::make_tuple(h, key);
+  });
+  m.def("hea_spec_load", [](int64_t handle) { check(qfx::hea_spec_load((int)handle), "qfx_hea_spec_load"); });
+  m.def("hea_spec_code", [](int64_t handle) {
+    const std::vector<char>* c = qfx::hea_spec_code((int)handle);
+    need(c != nullptr, "hea_spec_code: bad handle");
+    return pybind11::bytes(c->data(), c->size());
+  });
   m.def("hea_pass", &hea_pass, pybind11::arg("adjoint"), pybind11::arg("ops"), pybind11::arg("fidx"), pybind11::arg("fo"),
         pybind11::arg("geom"), pybind11::arg("scale"), pybind11::arg("psi_in"), pybind11::arg("psi_out"),
         pybind11::arg("lam_in"), pybind11::arg("lam_out"), pybind11::arg("xang"), pybind11::arg("params"),
         pybind11::arg("frags"), pybind11::arg("wread"), pybind11::arg("part"), pybind11::arg("gslab"),
-        pybind11::arg("dbg"), pybind11::arg("readout") = pybind11::none(), pybind11::arg("ro_tps") = 0);
+        pybind11::arg("dbg"), pybind11::arg("readout") = pybind11::none(), pybind11::arg("ro_tps") = 0,
+        pybind11::arg("spec") = -1);
   m.def("hea_frags", &hea_frags, pybind11::arg("params"), pybind11::arg("p_stride"), pybind11::arg("slot_tab"),
         pybind11::arg("n_slots"), pybind11::arg("K"), pybind11::arg("frags"), pybind11::arg("bf16") = false);
   m.def("hea_check_ops", &hea_check_ops);

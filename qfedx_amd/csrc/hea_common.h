@@ -3,11 +3,13 @@
 // hea_mfma_bf16.hip.  Storage-type primitives, op / record enums, fixed-point constants, stall-attribution stamps.
 #pragma once
 
+#ifndef __HIPCC_RTC__   // hiprtc (the per-plan build, hea_spec.cpp) brings the HIP device API itself and has no libstdc++
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#endif
 
 // Storage type of the states and unitary fragments: fp16 (this translation unit) or bf16 (hea_mfma_bf16.hip includes
 // this file with QFX_HEA_BF16=1: the same kernels in namespace hea_bf16, entry points suffixed _bf16).  Only the

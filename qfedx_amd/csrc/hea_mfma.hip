@@ -26,6 +26,77 @@ __device__ unsigned int qfx_check_word = 0;
 
 namespace HEA_NS {
 
+// ------------------------------------------------------------------------------------------- one source, two builds
+// The ahead-of-time build interprets any pass program: geometry in PassArgs, op records fetched through LDS.  The
+// per-plan build (QFX_HEA_SPEC, compiled by hiprtc from a generated prelude: csrc/hea_spec.cpp) runs ONE pass of ONE
+// plan: the prelude's namespace hea_spec holds that pass's geometry, op codes, counts, flags, fragment / gradient
+// indices and the XOR bases of every address table as constants.  Both builds share the pass bodies below through
+// two accessors:
+//   PA     the kernel argument.  Per-plan build: the geometry members are shadowed by constants (same layout, the
+//          host fills one HeaPassArgs for both paths), so a.t, a.hrow[b], ... fold at compile time.
+//   OpRec  one op's record.  Interpreter: words of the LDS copy.  Per-plan build: constants of op o, o a constant once
+//          the op loop is fully unrolled; a table entry is rebuilt from the table's XOR basis (the planner's tables
+//          are XOR-linear in their index: tab[i] = XOR_j bit_j(i) tab[1 << j]) - a few v_and / v_xor on lane bits, or
+//          scalar instructions for a wave-uniform index, and no memory access.
+#ifdef QFX_HEA_SPEC
+constexpr bool SPEC = true;
+#define HEA_OP_LOOP _Pragma("unroll")
+struct PA : PassArgs {
+  static constexpr int n = hea_spec::N, t = hea_spec::T, c = hea_spec::CB, lo = hea_spec::LO, hi = hea_spec::HI;
+  static constexpr int n_tiles = hea_spec::NTILES, nops = hea_spec::NOPS, C = hea_spec::NCLS;
+  static constexpr int gen = hea_spec::GEN, load_lam = hea_spec::LOAD_LAM, store_lam = hea_spec::STORE_LAM;
+  static constexpr int n_regions = hea_spec::NREG;
+  static constexpr const int (&hrow)[5] = hea_spec::HROW;
+};
+static_assert(sizeof(PA) == sizeof(PassArgs), "the per-plan kernel takes the interpreter's argument block");
+template <int NB>
+__device__ __forceinline__ uint32_t xlin(const unsigned* basis, int i) {
+  uint32_t r = 0;
+#pragma unroll
+  for (int j = 0; j < NB; ++j) r ^= (uint32_t)(-((i >> j) & 1)) & (uint32_t)basis[j];
+  return r;
+}
+struct OpRec {
+  int o;
+  __device__ __forceinline__ int code() const { return hea_spec::CODE[o]; }
+  __device__ __forceinline__ int nreal(int g = 0) const { return g ? hea_spec::NREAL2[o] : hea_spec::NREAL[o]; }
+  __device__ __forceinline__ int flags() const { return hea_spec::FLAGS[o]; }
+  __device__ __forceinline__ int gidx(int g = 0) const { return g ? hea_spec::GIDX2[o] : hea_spec::GIDX[o]; }
+  __device__ __forceinline__ int fidx(int g) const { return hea_spec::FIDX[o][g]; }
+  template <int TAB, class... I>
+  __device__ __forceinline__ uint32_t tab(I... ii) const {
+    const int i = (0 + ... + ii);
+    static_assert(TAB == W_OFF || TAB == W_OFF2 || TAB == W_BL || TAB == W_BH, "address tables");
+    if constexpr (TAB == W_OFF) return xlin<4>(hea_spec::OFFB[o], i);
+    if constexpr (TAB == W_OFF2) return xlin<4>(hea_spec::OFF2B[o], i);
+    if constexpr (TAB == W_BL) return xlin<5>(hea_spec::BLB[o], i);
+    return xlin<5>(hea_spec::BHB[o], i);
+  }
+  // observable / readout records: class c's tile-local and full masks
+  __device__ __forceinline__ uint32_t cls_om(int c) const { return hea_spec::CLS_OM[o][c]; }
+  __device__ __forceinline__ uint32_t cls_of(int c) const { return hea_spec::CLS_OF[o][c]; }
+};
+#else
+constexpr bool SPEC = false;
+#define HEA_OP_LOOP
+using PA = PassArgs;
+struct OpRec {
+  const int* w;
+  __device__ __forceinline__ int code() const { return w[W_CODE]; }
+  __device__ __forceinline__ int nreal(int g = 0) const { return w[g ? W_NREAL2 : W_NREAL]; }
+  __device__ __forceinline__ int flags() const { return w[W_FLAGS]; }
+  __device__ __forceinline__ int gidx(int g = 0) const { return w[g ? W_GIDX2 : W_GIDX]; }
+  // (the index terms are summed left to right onto the table's base, as the record reads were written before the
+  // accessor existed: the interpreter's object code depends on that association)
+  template <int TAB, class... I>
+  __device__ __forceinline__ uint32_t tab(I... i) const { return (uint32_t)w[(TAB + ... + i)]; }
+  __device__ __forceinline__ uint32_t cls_om(int c) const { return (uint32_t)__builtin_amdgcn_readfirstlane(w[W_OFF + c]); }
+  __device__ __forceinline__ uint32_t cls_of(int c) const {
+    return (uint32_t)__builtin_amdgcn_readfirstlane(w[W_RFULL + 2 * c]);
+  }
+};
+#endif
+
 // Pass-output tiles are stored with the non-temporal hint when a pass's states exceed the Infinity Cache (PassArgs::
 // nt_store, set by the host: 16q x 2048 samples = 512 MB per pass; the next pass reads them back from HBM anyway):
 // interleaved A/B, 64 clients 1.820 -> 1.784 ms per step; at 8 clients (64 MB, MALL-resident) the plain stores are
@@ -39,13 +110,13 @@ __device__ __forceinline__ void tile_st(uint32_t* p, uint4 v, int nt) {
 }
 
 // memory index of tile position tau
-__device__ __forceinline__ uint32_t mem_of(uint32_t tau, const PassArgs& a, uint32_t fixed) {
+__device__ __forceinline__ uint32_t mem_of(uint32_t tau, const PA& a, uint32_t fixed) {
   const uint32_t cm = (1u << a.c) - 1u;
   return (tau & cm) | ((tau >> a.c) << a.lo) | fixed;
 }
 
 // LDS swizzle h(x) (5 bank bits) of the high tile bits x = tau >> 5
-__device__ __forceinline__ uint32_t swz(const PassArgs& a, uint32_t x) {
+__device__ __forceinline__ uint32_t swz(const PA& a, uint32_t x) {
   uint32_t r = 0;
 #pragma unroll
   for (int b = 0; b < 5; ++b) r |= (uint32_t)par((uint32_t)a.hrow[b] & x) << b;
@@ -63,7 +134,7 @@ __device__ __forceinline__ uint4 quad_perm(uint4 v, uint32_t r) {
 // (q ^ h) & ~3 with its dwords permuted by h & 3, h = h(q >> 5) = h(tid >> 3) ^ h(4 NT / 32 * i).  All of a
 // thread's global loads are issued before its LDS writes.
 template <int NT, int TB = TMAX>
-__device__ __forceinline__ void load_tile(const PassArgs& a, const uint32_t* src, uint32_t* dst, int tid, int T,
+__device__ __forceinline__ void load_tile(const PA& a, const uint32_t* src, uint32_t* dst, int tid, int T,
                                           uint32_t h_q, uint32_t fixed) {
   constexpr int MQ = (1 << TB) / (4 * NT);
   uint4 v[MQ];
@@ -83,7 +154,7 @@ __device__ __forceinline__ void load_tile(const PassArgs& a, const uint32_t* src
 }
 
 template <int NT, int TB = TMAX>
-__device__ __forceinline__ void store_tile(const PassArgs& a, uint32_t* dst, const uint32_t* src, int tid, int T,
+__device__ __forceinline__ void store_tile(const PA& a, uint32_t* dst, const uint32_t* src, int tid, int T,
                                            uint32_t h_q, uint32_t fixed) {
   constexpr int MQ = (1 << TB) / (4 * NT);
   uint4 v[MQ];
@@ -108,7 +179,7 @@ __device__ __forceinline__ void store_tile(const PassArgs& a, uint32_t* dst, con
 // MFMA operands.  (Separate psi / lambda planes halve the bank conflicts but double the LDS instructions: measured
 // slower, round 3.)  Without a lambda input the lambda words are zeroed (the observable op writes them).
 template <int NT, int TB>
-__device__ __forceinline__ void load_tile_il(const PassArgs& a, const uint32_t* psrc, const uint32_t* lsrc,
+__device__ __forceinline__ void load_tile_il(const PA& a, const uint32_t* psrc, const uint32_t* lsrc,
                                              uint32_t* tile, int tid, int T, uint32_t h_q, uint32_t fixed) {
   constexpr int MQ = (1 << TB) / (4 * NT);
   uint4 v[MQ], l[MQ];
@@ -134,7 +205,7 @@ __device__ __forceinline__ void load_tile_il(const PassArgs& a, const uint32_t* 
 }
 
 template <int NT, int TB>
-__device__ __forceinline__ void store_lam_il(const PassArgs& a, uint32_t* dst, const uint32_t* tile, int tid, int T,
+__device__ __forceinline__ void store_lam_il(const PA& a, uint32_t* dst, const uint32_t* tile, int tid, int T,
                                              uint32_t h_q, uint32_t fixed) {
   constexpr int MQ = (1 << TB) / (4 * NT);
   uint4 v[MQ];
@@ -236,7 +307,7 @@ __device__ __forceinline__ uint32_t mul_i(uint32_t v) {
 //                (acc[0]: B = lambda, acc[1]: B = i lambda).  Accumulator layout as group_cross: lane (g4, cl)
 //                holds N[4 g4 + i][cl].
 template <int NW, bool ADJ, int TB = TMAX>
-__device__ __forceinline__ void group_apply(uint32_t* tile, const uint4* F, const int* opw, uint32_t fo, int lane,
+__device__ __forceinline__ void group_apply(uint32_t* tile, const uint4* F, const OpRec& opw, uint32_t fo, int lane,
                                             int wave, int nbw, f4* acc = nullptr) {
   constexpr int MAXB = (1 << (TB - 8)) / NW;   // column blocks per wave per op (t = 14: 64 blocks)
   constexpr int NL = ADJ ? 2 : 1;              // registers loaded per block: psi and lambda for the cross
@@ -244,7 +315,7 @@ __device__ __forceinline__ void group_apply(uint32_t* tile, const uint4* F, cons
   const int g4 = lane >> 4, cl = lane & 15;
   uint32_t oin[4];
 #pragma unroll
-  for (int jj = 0; jj < 4; ++jj) oin[jj] = ((uint32_t)opw[W_OFF + 4 * g4 + jj] ^ fo) << SH;
+  for (int jj = 0; jj < 4; ++jj) oin[jj] = (opw.tab<W_OFF>(4 * g4, jj) ^ fo) << SH;
   // identity fragments (rows: re of amplitude n, then im), built here from an opaque copy of the lane index so the
   // compiler cannot hoist them out of the kernel's op loop (hoisted, they were spilled to scratch there)
   uint4 IRE = {}, IIM = {};
@@ -260,10 +331,10 @@ __device__ __forceinline__ void group_apply(uint32_t* tile, const uint4* F, cons
       im[j] = dg == j ? ONE_HI : 0u;
     }
   }
-  const uint32_t bl = (uint32_t)opw[W_BL + (wave & 1) * 16 + cl];
+  const uint32_t bl = opw.tab<W_BL>((wave & 1) * 16, cl);
   uint32_t base[MAXB];
 #pragma unroll
-  for (int i = 0; i < MAXB; ++i) base[i] = (bl ^ (uint32_t)opw[W_BH + ((wave + NW * i) >> 1)]) << SH;
+  for (int i = 0; i < MAXB; ++i) base[i] = (bl ^ opw.tab<W_BH>(((wave + NW * i) >> 1))) << SH;
   auto load = [&](uint32_t b, uint4* X) {
     const uint32_t a0 = b ^ oin[0], a1 = b ^ oin[1], a2 = b ^ oin[2], a3 = b ^ oin[3];
     if constexpr (ADJ) {
@@ -330,18 +401,18 @@ __device__ __forceinline__ void group_apply(uint32_t* tile, const uint4* F, cons
 // K = 16 columns x (re, im), lane (g4, cl) reads amplitude m = cl of columns 4 g4 .. 4 g4 + 3; accR / accI
 // end up holding N[4 g4 + i][cl] (real / imaginary).
 template <int NW, int TB = TMAX>
-__device__ __forceinline__ void group_cross(const uint32_t* tile, const int* opw, uint32_t fo, int lane, int wave,
+__device__ __forceinline__ void group_cross(const uint32_t* tile, const OpRec& opw, uint32_t fo, int lane, int wave,
                                             int nbw, f4& accR, f4& accI) {
   constexpr int MAXB = (1 << (TB - 8)) / NW;
   const int g4 = lane >> 4, cl = lane & 15;
-  const uint32_t om = (uint32_t)opw[W_OFF + cl] ^ fo;
+  const uint32_t om = opw.tab<W_OFF>(cl) ^ fo;
   uint32_t gb[4];
 #pragma unroll
-  for (int jj = 0; jj < 4; ++jj) gb[jj] = ((uint32_t)opw[W_BL + (wave & 1) * 16 + 4 * g4 + jj] ^ om) << 3;
+  for (int jj = 0; jj < 4; ++jj) gb[jj] = (opw.tab<W_BL>((wave & 1) * 16, 4 * g4, jj) ^ om) << 3;
 #pragma unroll
   for (int i = 0; i < MAXB; ++i) {
     if (i >= nbw) break;
-    const uint32_t bh = (uint32_t)opw[W_BH + ((wave + NW * i) >> 1)] << 3;
+    const uint32_t bh = opw.tab<W_BH>(((wave + NW * i) >> 1)) << 3;
     uint32_t pv[4], lv[4];
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {            // psi and lambda of one amplitude: one b64 pair
@@ -370,21 +441,21 @@ __device__ __forceinline__ void group_cross(const uint32_t* tile, const int* opw
 // results go back amplitude-major: lane (g4, cl) writes amplitude cl of columns 4 g4 .. 4 g4 + 3, one 16-lane
 // b64 store group = 16 amplitudes of one column (the planner keeps their pair banks distinct).
 template <int NW, int TB>
-__device__ __forceinline__ void group_back_t(uint32_t* tile, const uint4* F, const int* opw, uint32_t fo, int lane,
+__device__ __forceinline__ void group_back_t(uint32_t* tile, const uint4* F, const OpRec& opw, uint32_t fo, int lane,
                                              int wave, int nbw, f4* acc) {
   constexpr int MAXB = (1 << (TB - 8)) / NW;
   constexpr int SH = 3;
   const int g4 = lane >> 4, cl = lane & 15;
   // load address of block i, amplitude 4 g4 + j: lo[j] ^ bh[i]; store address of column 4 g4 + r: ost[r] ^ bh[i]
   uint32_t lo[4], ost[4], bh[MAXB];
-  const uint32_t om = (uint32_t)opw[W_OFF + cl] ^ fo, bl = (uint32_t)opw[W_BL + (wave & 1) * 16 + cl] ^ fo;
+  const uint32_t om = opw.tab<W_OFF>(cl) ^ fo, bl = opw.tab<W_BL>((wave & 1) * 16, cl) ^ fo;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    lo[j] = ((uint32_t)opw[W_OFF + 4 * g4 + j] ^ bl) << SH;
-    ost[j] = ((uint32_t)opw[W_BL + (wave & 1) * 16 + 4 * g4 + j] ^ om) << SH;
+    lo[j] = (opw.tab<W_OFF>(4 * g4, j) ^ bl) << SH;
+    ost[j] = (opw.tab<W_BL>((wave & 1) * 16, 4 * g4, j) ^ om) << SH;
   }
 #pragma unroll
-  for (int i = 0; i < MAXB; ++i) bh[i] = (uint32_t)opw[W_BH + ((wave + NW * i) >> 1)] << SH;
+  for (int i = 0; i < MAXB; ++i) bh[i] = opw.tab<W_BH>(((wave + NW * i) >> 1)) << SH;
   auto load = [&](int i, uint4* X) {
     const uint32_t b = bh[i];
     const uint2 p0 = lds_ld2(tile, b ^ lo[0]), p1 = lds_ld2(tile, b ^ lo[1]), p2 = lds_ld2(tile, b ^ lo[2]),
@@ -451,7 +522,7 @@ __device__ __forceinline__ void group_back_t(uint32_t* tile, const uint4* F, con
 // embedding are i times them per (re, im) word (frag_regs).  A pair op's second group fills the slot's upper half.
 // The LDS base of a wave-instruction is wave-uniform (M0); the DMA is complete once wave 0 has passed
 // s_waitcnt vmcnt(0) (op_barrier).
-__device__ __forceinline__ void dma_frags(const PassArgs& a, int k, const int* fi, int lane, int wave, uint4* slot) {
+__device__ __forceinline__ void dma_frags(const PA& a, int k, const int* fi, int lane, int wave, uint4* slot) {
   if (wave != 0) return;
 #pragma unroll
   for (int g = 0; g < 2; ++g) {
@@ -498,20 +569,20 @@ __device__ __forceinline__ void frag_regs(const uint4* slot, int g, int lane, ui
 // Per-lane address words of a pair op (byte offsets, SH = log2 bytes per amplitude image entry):
 //   xa[j] = (x = 4 g4 + j, y = cl),   ya[j] = (x = cl, y = 4 g4 + j)
 template <int SH>
-__device__ __forceinline__ void pair_addrs(const int* opw, uint32_t fo, int lane, uint32_t* xa, uint32_t* ya) {
+__device__ __forceinline__ void pair_addrs(const OpRec& opw, uint32_t fo, int lane, uint32_t* xa, uint32_t* ya) {
   const int g4 = lane >> 4, cl = lane & 15;
-  const uint32_t ox = (uint32_t)opw[W_OFF + cl], oy = (uint32_t)opw[W_OFF2 + cl];
+  const uint32_t ox = opw.tab<W_OFF>(cl), oy = opw.tab<W_OFF2>(cl);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    xa[j] = ((uint32_t)opw[W_OFF + 4 * g4 + j] ^ oy ^ fo) << SH;
-    ya[j] = (ox ^ (uint32_t)opw[W_OFF2 + 4 * g4 + j] ^ fo) << SH;
+    xa[j] = (opw.tab<W_OFF>(4 * g4, j) ^ oy ^ fo) << SH;
+    ya[j] = (ox ^ opw.tab<W_OFF2>(4 * g4, j) ^ fo) << SH;
   }
 }
 
 // block blk's coset base (byte offset)
 template <int SH>
-__device__ __forceinline__ uint32_t pair_base(const int* opw, int blk) {
-  return ((uint32_t)opw[W_BL + (blk & 31)] ^ (uint32_t)opw[W_BH + (blk >> 5)]) << SH;
+__device__ __forceinline__ uint32_t pair_base(const OpRec& opw, int blk) {
+  return (opw.tab<W_BL>((blk & 31)) ^ opw.tab<W_BH>((blk >> 5))) << SH;
 }
 
 __device__ __forceinline__ uint4 pack4(const f4& re, const f4& im) {
@@ -522,7 +593,7 @@ __device__ __forceinline__ uint4 pack4(const f4& re, const f4& im) {
 // A wave owns blocks blk = wave + NW i; the next block's reads are issued before the current block computes (all of
 // a block's addresses belong to its coset, so blocks are disjoint).
 template <int NW, int TB>
-__device__ __forceinline__ void group_pair_fwd(uint32_t* tile, const uint4* FX, const uint4* FY, const int* opw,
+__device__ __forceinline__ void group_pair_fwd(uint32_t* tile, const uint4* FX, const uint4* FY, const OpRec& opw,
                                                uint32_t fo, int lane, int wave, int nbw) {
   constexpr int MAXB = (1 << (TB - 8)) / NW;
   uint32_t xa[4], ya[4];
@@ -561,7 +632,7 @@ __device__ __forceinline__ void group_pair_fwd(uint32_t* tile, const uint4* FX, 
 // matrix taken from its rounded results (the op input side, as group_back_t): acc[0..1] for X, acc[2..3] for Y.  Read
 // and written at the same addresses (x = 4 g4 + j, y = cl): after Y the lane holds y = cl for x = 4 g4 + r.
 template <int NW, int TB>
-__device__ __forceinline__ void group_pair_back(uint32_t* tile, const uint4* FX, const uint4* FY, const int* opw,
+__device__ __forceinline__ void group_pair_back(uint32_t* tile, const uint4* FX, const uint4* FY, const OpRec& opw,
                                                 uint32_t fo, int lane, int wave, int nbw, f4* acc) {
   constexpr int MAXB = (1 << (TB - 8)) / NW;
   uint32_t xa[4], ya[4];
@@ -628,7 +699,7 @@ __device__ __forceinline__ void group_pair_back(uint32_t* tile, const uint4* FX,
 // Cross-matrix-only pair (layer-1 gradient groups): N_X from the reads at (x = cl, y = 4 g4 + j) (columns y in K),
 // N_Y from (x = 4 g4 + j, y = cl); read-only, so both address patterns read the same coset with no barrier between.
 template <int NW, int TB>
-__device__ __forceinline__ void group_pair_cross(const uint32_t* tile, const int* opw, uint32_t fo, int lane, int wave,
+__device__ __forceinline__ void group_pair_cross(const uint32_t* tile, const OpRec& opw, uint32_t fo, int lane, int wave,
                                                  int nbw, f4* acc) {
   constexpr int MAXB = (1 << (TB - 8)) / NW;
   uint32_t xa[4], ya[4];
@@ -686,7 +757,7 @@ struct ClassSigns {
 };
 
 template <int NC, int NT, int CH, int TB = TMAX>
-__device__ __forceinline__ ClassSigns<NC, CH> class_signs(const int* opw, int tid, uint32_t fixed, int iters) {
+__device__ __forceinline__ ClassSigns<NC, CH> class_signs(const OpRec& opw, int tid, uint32_t fixed, int iters) {
   constexpr int QI = (1 << TB) / NT;
   static_assert((QI / CH) * NC <= 32 && CH * NC <= 64, "class sign masks must fit one / two dwords");
   ClassSigns<NC, CH> cs;
@@ -696,8 +767,8 @@ __device__ __forceinline__ ClassSigns<NC, CH> class_signs(const int* opw, int ti
   cs.iters = iters;
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
-    const uint32_t om = (uint32_t)__builtin_amdgcn_readfirstlane(opw[W_OFF + c]);
-    const uint32_t of = (uint32_t)__builtin_amdgcn_readfirstlane(opw[W_RFULL + 2 * c]);
+    const uint32_t om = opw.cls_om(c);
+    const uint32_t of = opw.cls_of(c);
     cs.sgn0 |= (uint32_t)(par((uint32_t)tid & om) ^ par(fixed & of)) << c;
 #pragma unroll
     for (int k = 0; k < QI / CH; ++k) cs.fu |= (uint32_t)par((uint32_t)(NT * CH * k) & om) << (k * NC + c);
@@ -715,7 +786,7 @@ __device__ __forceinline__ ClassSigns<NC, CH> class_signs(const int* opw, int ti
 
 // <Z_c> partial sums of the tile (forward image: one fp16 (re, im) word per amplitude).
 template <int NC, int NT>
-__device__ __forceinline__ void readout_op(const uint32_t* psi_t, const PassArgs& a, const int* opw, int tid,
+__device__ __forceinline__ void readout_op(const uint32_t* psi_t, const PA& a, const OpRec& opw, int tid,
                                            int lane, int wave, int T, uint32_t fixed, float* red, size_t pidx) {
   constexpr int QI = (1 << TMAX) / NT, NW = NT / 64;
   constexpr int CH = QI < RCH ? QI : RCH;
@@ -758,7 +829,7 @@ __device__ __forceinline__ void readout_op(const uint32_t* psi_t, const PassArgs
 
 // Adjoint seed lambda = sum_c r_c Z_c psi on the interleaved adjoint image (psi word 2w, lambda word 2w + 1).
 template <int NC, int NT, int TB = TMAX>
-__device__ __forceinline__ void obs_op(uint32_t* tile, const int* opw, int tid, int T, uint32_t fixed,
+__device__ __forceinline__ void obs_op(uint32_t* tile, const OpRec& opw, int tid, int T, uint32_t fixed,
                                        const float* rsc_s) {
   constexpr int QI = (1 << TB) / NT;
   constexpr int CH = QI < RCH ? QI : RCH;
@@ -808,7 +879,7 @@ __device__ __forceinline__ void op_barrier(int wave) {
 }
 
 // Memory bits of tile tile_id outside the tile.
-__device__ __forceinline__ uint32_t tile_fixed(const PassArgs& a, int tile_id) {
+__device__ __forceinline__ uint32_t tile_fixed(const PA& a, int tile_id) {
   const int w1 = a.lo - a.c;
   return ((uint32_t)(tile_id & ((1 << w1) - 1)) << a.c) | ((uint32_t)(tile_id >> w1) << a.hi);
 }
@@ -837,11 +908,13 @@ __device__ __forceinline__ uint32_t op_fo_global(const int* ow, uint32_t fixed) 
 // One workgroup per tile of 2^t <= 2^14 amplitudes: 8 waves and 64 KB of LDS, so two workgroups share a CU and
 // one's tile load overlaps the other's group ops (minimum waves per SIMD 4: <= 128 VGPRs).
 template <int NCK, bool FULL>
-__device__ __forceinline__ void fwd_pass(const PassArgs& a, int bid) {
+__device__ __forceinline__ void fwd_pass(const PA& a, int bid) {
   constexpr int NT = NT_FWD, NW = NT / 64;
   __shared__ __attribute__((aligned(16))) uint32_t psi_t[1 << TMAX];   // fp16 (re, im), swizzled
+#ifndef QFX_HEA_SPEC   // (per-plan build: the records and fragment indices are compile-time constants)
   __shared__ int opw2[2][OPW];                          // op records, double buffered (one barrier per op)
   __shared__ int fidx_s[MAXOPS][2];                     // per-op fragment indices (pair ops: two), staged once
+#endif
   __shared__ uint32_t fo_s[MAXOPS];                     // per-op OFF base of this tile (fo_tab)
   __shared__ __attribute__((aligned(16))) uint4 frag_s[2][256];   // op unitary fragments, double buffered
   __shared__ float red[NW * CMAX];
@@ -868,14 +941,23 @@ __device__ __forceinline__ void fwd_pass(const PassArgs& a, int bid) {
   // op records and unitary fragments are prefetched one op ahead (their global latency hides behind an op); op 0's
   // are requested before the initial tile, so their latency hides behind the tile load / layer-1 generation
   if (tid < a.nops) {                            // LDS copies: the prefetch below never waits on a global load
+#ifndef QFX_HEA_SPEC
     fidx_s[tid][0] = a.fidx[2 * tid];
     fidx_s[tid][1] = a.fidx[2 * tid + 1];
+#endif
     fo_s[tid] = a.fo_tab[(size_t)tile_id * a.nops + tid];
     QFX_DCHECK(fo_s[tid] == op_fo_global(a.ops + (size_t)tid * OPW, fixed));
   }
+#ifdef QFX_HEA_SPEC
+  if (a.nops > 0) {
+    const int fi0[2] = {OpRec{0}.fidx(0), OpRec{0}.fidx(1)};
+    dma_frags(a, k, fi0, lane, wave, frag_s[0]);
+  }
+#else
   if (tid < OPW && a.nops > 0) opw2[0][tid] = a.ops[tid];
   int nxt = (tid < OPW && a.nops > 1) ? a.ops[OPW + tid] : 0;
   if (a.nops > 0) dma_frags(a, k, a.fidx, lane, wave, frag_s[0]);
+#endif
   st.mark(PH_PRO);
 
   // ---------------------------------------------------------------- initial psi tile
@@ -959,6 +1041,7 @@ __device__ __forceinline__ void fwd_pass(const PassArgs& a, int bid) {
   st.mark(PH_LOAD);
   op_barrier(wave);   // (waves 0-1 wait for op 0's fragment DMA and record loads; the readout wave's stores never)
   st.mark(PH_BAR);
+  HEA_OP_LOOP
   for (int o = 0; o < a.nops; ++o) {
     // op o's record and fragments were written during op o - 1; the other buffers were last read at the
     // start of op o - 1, which every wave has finished at this barrier, so op o + 1's go there right away
@@ -966,8 +1049,17 @@ __device__ __forceinline__ void fwd_pass(const PassArgs& a, int bid) {
       op_barrier(wave);
       st.mark(PH_BAR);
     }
-    const int* opw = opw2[o & 1];
     uint4 F[4], FY[4];
+#ifdef QFX_HEA_SPEC
+    const OpRec opw{o};
+    if (opw.fidx(0) >= 0) frag_regs(frag_s[o & 1], 0, lane, F);
+    if (opw.fidx(1) >= 0) frag_regs(frag_s[o & 1], 1, lane, FY);
+    if (o + 1 < a.nops) {
+      const int fin[2] = {OpRec{o + 1 < a.nops ? o + 1 : o}.fidx(0), OpRec{o + 1 < a.nops ? o + 1 : o}.fidx(1)};
+      dma_frags(a, k, fin, lane, wave, frag_s[(o + 1) & 1]);
+    }
+#else
+    const OpRec opw{opw2[o & 1]};
     if (fidx_s[o][0] >= 0) frag_regs(frag_s[o & 1], 0, lane, F);
     if (fidx_s[o][1] >= 0) frag_regs(frag_s[o & 1], 1, lane, FY);
     if (o + 1 < a.nops) {
@@ -975,21 +1067,22 @@ __device__ __forceinline__ void fwd_pass(const PassArgs& a, int bid) {
       if (o + 2 < a.nops && tid < OPW) nxt = a.ops[(size_t)(o + 2) * OPW + tid];
       dma_frags(a, k, fidx_s[o + 1], lane, wave, frag_s[(o + 1) & 1]);
     }
-    const int code = opw[W_CODE];
+#endif
+    const int code = opw.code();
 #if QFX_CHECKS_ON
     QFX_DCHECK(code == OP_APPLY || code == OP_APPLY2 || code == OP_READOUT);
     if (code != OP_READOUT) {
-      QFX_DCHECK(opw[W_NREAL] >= 0 && opw[W_NREAL] <= 4);
-      QFX_DCHECK((uint32_t)opw[W_OFF + (lane & 15)] < (uint32_t)T);
-      QFX_DCHECK((uint32_t)opw[W_BL + (lane & 31)] < (uint32_t)T);
-      QFX_DCHECK((uint32_t)opw[W_BH + (lane & 31)] < (uint32_t)T);
+      QFX_DCHECK(opw.nreal() >= 0 && opw.nreal() <= 4);
+      QFX_DCHECK(opw.tab<W_OFF>((lane & 15)) < (uint32_t)T);
+      QFX_DCHECK(opw.tab<W_BL>((lane & 31)) < (uint32_t)T);
+      QFX_DCHECK(opw.tab<W_BH>((lane & 31)) < (uint32_t)T);
       QFX_DCHECK(fidx_s[o][0] >= 0 && fidx_s[o][0] < 4 * a.n_slots);
       if (code == OP_APPLY2) {
-        QFX_DCHECK((uint32_t)opw[W_OFF2 + (lane & 15)] < (uint32_t)T);
+        QFX_DCHECK(opw.tab<W_OFF2>((lane & 15)) < (uint32_t)T);
         QFX_DCHECK(fidx_s[o][1] >= 0 && fidx_s[o][1] < 4 * a.n_slots && a.t >= 11);
       }
     } else {
-      QFX_DCHECK(opw[W_NREAL] >= 1 && opw[W_NREAL] <= a.C);
+      QFX_DCHECK(opw.nreal() >= 1 && opw.nreal() <= a.C);
     }
 #endif
     st.mark(PH_SETUP);
@@ -1026,13 +1119,15 @@ __device__ __forceinline__ void fwd_pass(const PassArgs& a, int bid) {
 // 2^(TB - 10) waves give each wave 4 column blocks per op (a 4-wave 2^13 workgroup with 8 blocks per wave halves the
 // per-op setup per MFMA but halves the waves per SIMD: measured 18% slower, round 4).
 template <int NCK, int TB, bool FULL>
-__device__ __forceinline__ void adj_pass(const PassArgs& a, int bid) {
+__device__ __forceinline__ void adj_pass(const PA& a, int bid) {
   constexpr int NT = 1 << (TB - 4), NW = NT / 64;
   static_assert(NW % 2 == 0 && (1 << (TB - 8)) % NW == 0, "column blocks per wave must be whole, block pairs aligned");
   // (psi, lambda) pairs (fp16 re, im), swizzled; 16-byte aligned for the b64 / b128 accesses
   __shared__ __attribute__((aligned(16))) uint32_t tile[2 << TB];
+#ifndef QFX_HEA_SPEC   // (per-plan build: the records and fragment indices are compile-time constants)
   __shared__ int opw2[2][OPW];                          // op records, double buffered (one barrier per op)
   __shared__ int fidx_s[MAXOPS][2];                     // per-op fragment indices (pair ops: two), staged once
+#endif
   __shared__ uint32_t fo_s[MAXOPS];                     // per-op OFF base of this tile (fo_tab)
   __shared__ __attribute__((aligned(16))) uint4 frag_s[2][256];   // op unitary fragments, double buffered
   // the 80 cross-matrix entries a partial trace can use (b = a, and b = a ^ e_j) x (re, im), 2^-32 fixed point
@@ -1061,14 +1156,23 @@ __device__ __forceinline__ void adj_pass(const PassArgs& a, int bid) {
 
   // op 0's record and fragments are requested before the tile load (their latency hides behind it)
   if (tid < a.nops) {
+#ifndef QFX_HEA_SPEC
     fidx_s[tid][0] = a.fidx[2 * tid];
     fidx_s[tid][1] = a.fidx[2 * tid + 1];
+#endif
     fo_s[tid] = a.fo_tab[(size_t)tile_id * a.nops + tid];
     QFX_DCHECK(fo_s[tid] == op_fo_global(a.ops + (size_t)tid * OPW, fixed));
   }
+#ifdef QFX_HEA_SPEC
+  if (a.nops > 0) {
+    const int fi0[2] = {OpRec{0}.fidx(0), OpRec{0}.fidx(1)};
+    dma_frags(a, k, fi0, lane, wave, frag_s[0]);
+  }
+#else
   if (tid < OPW && a.nops > 0) opw2[0][tid] = a.ops[tid];
   int nxt = (tid < OPW && a.nops > 1) ? a.ops[OPW + tid] : 0;
   if (a.nops > 0) dma_frags(a, k, a.fidx, lane, wave, frag_s[0]);
+#endif
   // Fused readout (the last wave): its lanes load the sample's readout partials, label, loss weight and readout
   // parameters BEFORE the tile load is issued, so their latency overlaps the tile's; lane 0 sums the partials in tile
   // order after the load (the readout kernel's order and arithmetic, qfx_readout.h).
@@ -1193,6 +1297,7 @@ __device__ __forceinline__ void adj_pass(const PassArgs& a, int bid) {
                                                     : 0xFFu;
     epi |= sl << (8 * i);
   }
+  HEA_OP_LOOP
   for (int o = 0; o < a.nops; ++o) {
     // op o's record and fragments were written during op o - 1; the other buffers were last read at the
     // start of op o - 1, which every wave has finished at this barrier, so op o + 1's go there right away
@@ -1205,8 +1310,17 @@ __device__ __forceinline__ void adj_pass(const PassArgs& a, int bid) {
         if (wave == NW - 1 - q) flush((pending + q) & 3);
       npend = 0;
     }
-    const int* opw = opw2[o & 1];
     uint4 F[4], FY[4];
+#ifdef QFX_HEA_SPEC
+    const OpRec opw{o};
+    if (opw.fidx(0) >= 0) frag_regs(frag_s[o & 1], 0, lane, F);
+    if (opw.fidx(1) >= 0) frag_regs(frag_s[o & 1], 1, lane, FY);
+    if (o + 1 < a.nops) {
+      const int fin[2] = {OpRec{o + 1 < a.nops ? o + 1 : o}.fidx(0), OpRec{o + 1 < a.nops ? o + 1 : o}.fidx(1)};
+      dma_frags(a, k, fin, lane, wave, frag_s[(o + 1) & 1]);
+    }
+#else
+    const OpRec opw{opw2[o & 1]};
     if (fidx_s[o][0] >= 0) frag_regs(frag_s[o & 1], 0, lane, F);
     if (fidx_s[o][1] >= 0) frag_regs(frag_s[o & 1], 1, lane, FY);
     if (o + 1 < a.nops) {
@@ -1214,26 +1328,27 @@ __device__ __forceinline__ void adj_pass(const PassArgs& a, int bid) {
       if (o + 2 < a.nops && tid < OPW) nxt = a.ops[(size_t)(o + 2) * OPW + tid];
       dma_frags(a, k, fidx_s[o + 1], lane, wave, frag_s[(o + 1) & 1]);
     }
-    const int code = opw[W_CODE];
+#endif
+    const int code = opw.code();
 #if QFX_CHECKS_ON
     QFX_DCHECK(code == OP_BACK || code == OP_GRAD_L1 || code == OP_OBS || code == OP_BACK2 || code == OP_GRAD2);
     if (code != OP_OBS) {
       const bool pr2 = code == OP_BACK2 || code == OP_GRAD2;
-      QFX_DCHECK(opw[W_NREAL] >= 0 && opw[W_NREAL] <= 4);
-      QFX_DCHECK((uint32_t)opw[W_OFF + (lane & 15)] < (uint32_t)T);
-      QFX_DCHECK((uint32_t)opw[W_BL + (lane & 31)] < (uint32_t)T);
-      QFX_DCHECK((uint32_t)opw[W_BH + (lane & 31)] < (uint32_t)T);
+      QFX_DCHECK(opw.nreal() >= 0 && opw.nreal() <= 4);
+      QFX_DCHECK(opw.tab<W_OFF>((lane & 15)) < (uint32_t)T);
+      QFX_DCHECK(opw.tab<W_BL>((lane & 31)) < (uint32_t)T);
+      QFX_DCHECK(opw.tab<W_BH>((lane & 31)) < (uint32_t)T);
       // -1 = no unitary (cross-matrix-only gradient ops); every op that applies one names a fragment
       QFX_DCHECK(fidx_s[o][0] >= -1 && fidx_s[o][0] < 4 * a.n_slots);
       QFX_DCHECK(fidx_s[o][0] >= 0 || code == OP_GRAD_L1 || code == OP_GRAD2);
-      QFX_DCHECK(opw[W_GIDX] >= 0 && opw[W_GIDX] < a.n_gradops);
+      QFX_DCHECK(opw.gidx() >= 0 && opw.gidx() < a.n_gradops);
       if (pr2) {
-        QFX_DCHECK((uint32_t)opw[W_OFF2 + (lane & 15)] < (uint32_t)T && a.t >= 11);
-        QFX_DCHECK(opw[W_GIDX2] >= 0 && opw[W_GIDX2] < a.n_gradops);
+        QFX_DCHECK(opw.tab<W_OFF2>((lane & 15)) < (uint32_t)T && a.t >= 11);
+        QFX_DCHECK(opw.gidx(1) >= 0 && opw.gidx(1) < a.n_gradops);
         QFX_DCHECK(code == OP_GRAD2 || (fidx_s[o][1] >= 0 && fidx_s[o][1] < 4 * a.n_slots));
       }
     } else {
-      QFX_DCHECK(opw[W_NREAL] >= 1 && opw[W_NREAL] <= a.C);
+      QFX_DCHECK(opw.nreal() >= 1 && opw.nreal() <= a.C);
     }
 #endif
     st.mark(PH_SETUP);
@@ -1244,7 +1359,7 @@ __device__ __forceinline__ void adj_pass(const PassArgs& a, int bid) {
       const uint32_t fo = fo_s[o];
       f4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
       int ng = 1;
-      if (code == OP_BACK && (opw[W_FLAGS] & F_BACK_PSI)) {
+      if (code == OP_BACK && (opw.flags() & F_BACK_PSI)) {
         // U^H on psi and lambda, cross matrix at the op input from the results (hea_grad_reduce: input side)
         group_back_t<NW, TB>(tile, F, opw, fo, lane, wave, nbw, acc);
         st.mark(PH_BACK);
@@ -1291,8 +1406,8 @@ __device__ __forceinline__ void adj_pass(const PassArgs& a, int bid) {
           }
         }
         if (tid == 0) {
-          gmeta_s[reg][0] = opw[g ? W_GIDX2 : W_GIDX];
-          gmeta_s[reg][1] = opw[g ? W_NREAL2 : W_NREAL];   // (a layer-1 pair's groups may be short)
+          gmeta_s[reg][0] = opw.gidx(g);
+          gmeta_s[reg][1] = opw.nreal(g);   // (a layer-1 pair's groups may be short)
         }
         ++ngrad;
       }
@@ -1314,6 +1429,19 @@ __device__ __forceinline__ void adj_pass(const PassArgs& a, int bid) {
 }
 
 // ------------------------------------------------------------------------------------------- launches
+#ifdef QFX_HEA_SPEC
+// Per-plan build: one entry point, this pass's kernel.  Workgroup shape and tile size class as the interpreter's
+// launch picks them (HEA_LAUNCH below); a tile that fills its size class has compile-time block counts (FULL).
+constexpr int SPEC_TB = hea_spec::ADJ ? (hea_spec::T <= 13 ? 13 : 14) : TMAX;
+constexpr int SPEC_NT = hea_spec::ADJ ? (1 << (SPEC_TB - 4)) : NT_FWD;
+extern "C" __global__ void __launch_bounds__(SPEC_NT, hea_spec::ADJ ? SPEC_NT * 2 / 256 : 4) qfx_hea_spec_pass(PA a) {
+  constexpr int NCK = class_kernel(hea_spec::NCLS);
+  if constexpr (hea_spec::ADJ)
+    adj_pass<NCK, SPEC_TB, SPEC_TB == 14>(a, blockIdx.x);
+  else
+    fwd_pass<NCK, hea_spec::T == TMAX>(a, blockIdx.x);
+}
+#else
 template <int NCK, bool FULL>
 __global__ void __launch_bounds__(NT_FWD, 4) hea_fwd_kernel(PassArgs a) { fwd_pass<NCK, FULL>(a, blockIdx.x); }
 
@@ -1321,8 +1449,11 @@ template <int NCK, int TB, bool FULL>
 __global__ void __launch_bounds__(1 << (TB - 4), (1 << (TB - 4)) * 2 / 256) hea_adj_kernel(PassArgs a) {
   adj_pass<NCK, TB, FULL>(a, blockIdx.x);
 }
+#endif
 
 }  // namespace HEA_NS
+
+#ifndef QFX_HEA_SPEC   // host launch code: the ahead-of-time build only
 
 // adjoint: 2^13 tiles (8 waves, two workgroups per CU) up to t = 13, else one 16-wave 2^14 workgroup per CU
 #define HEA_LAUNCH(NCK, KF, KA, ARG)                                                                         \
@@ -1382,3 +1513,4 @@ extern "C" int HEA_EXT(qfx_hea_check_status)(hipStream_t st) {
   return -1;
 #endif
 }
+#endif  // !QFX_HEA_SPEC

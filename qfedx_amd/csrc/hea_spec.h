@@ -1,0 +1,33 @@
+// Per-plan build of the MFMA pass kernels (hea_spec.cpp): what the bindings pass in and call.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "hea_args.h"
+
+namespace qfx {
+
+// One pass program and the constants its kernel is compiled with.
+struct HeaSpecDesc {
+  bool adjoint = false, bf16 = false, stamps = false;
+  int gate_lo = -1;                 // -1: the source's default (QFX_HEA_GATE_LO)
+  int n = 0, t = 0, c = 0, lo = 0, hi = 0, ncls = 0;
+  int gen = 0, load_lam = 0, store_lam = 0, n_regions = 0;
+  int hrow[5] = {0, 0, 0, 0, 0};
+  std::vector<int> ops;             // [nops][128] op records
+  std::vector<int> fidx;            // [nops][2] fragment indices
+};
+
+std::string hea_spec_prelude(const HeaSpecDesc& d);
+std::string hea_spec_source(const HeaSpecDesc& d);
+std::string hea_spec_key(const HeaSpecDesc& d, const std::string& include_dir, const std::string& arch);
+int hea_spec_prepare(const HeaSpecDesc& d, const std::string& cache_dir, const std::string& include_dir,
+                     const std::string& arch, std::string* key_out);
+int hea_spec_load(int handle);
+int hea_spec_launch(int handle, int adjoint, bool bf16, const HeaPassArgs* args, int n_samples, hipStream_t st);
+const std::vector<char>* hea_spec_code(int handle);
+
+}  // namespace qfx

@@ -27,26 +27,12 @@
 #include <unordered_map>
 #include <vector>
 
+#include "jit_util.h"
 #include "qfx_plan.h"
 
 namespace qfx {
 
 namespace {
-
-std::string hex64(uint64_t h) {
-  char b[17];
-  std::snprintf(b, sizeof(b), "%016llx", (unsigned long long)h);
-  return b;
-}
-
-uint64_t fnv1a(const std::string& s) {
-  uint64_t h = 1469598103934665603ull;
-  for (unsigned char c : s) {
-    h ^= c;
-    h *= 1099511628211ull;
-  }
-  return h;
-}
 
 bool is_diag_kind(int k) {
   return k == K_RZ || k == K_P || k == K_Z || k == K_S || k == K_SDG || k == K_T || k == K_TDG;
@@ -457,30 +443,7 @@ JitSpec codegen_pass(const std::vector<int>& blob, int p, bool adjoint, bool bf1
   return spec;
 }
 
-// ------------------------------------------------------------------------------ compile + cache
-std::vector<char> hiprtc_compile(const std::string& src, const std::string& include_dir, const std::string& arch) {
-  hiprtcProgram prog;
-  if (hiprtcCreateProgram(&prog, src.c_str(), "qfx_jit.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS)
-    throw std::runtime_error("hiprtcCreateProgram failed");
-  std::string a = "--offload-arch=" + arch, inc = "-I" + include_dir;
-  const char* opts[] = {a.c_str(), inc.c_str(), "-O3", "-std=c++17"};
-  hiprtcResult rc = hiprtcCompileProgram(prog, 4, opts);
-  if (rc != HIPRTC_SUCCESS) {
-    size_t ls = 0;
-    hiprtcGetProgramLogSize(prog, &ls);
-    std::string log(ls, '\0');
-    hiprtcGetProgramLog(prog, &log[0]);
-    hiprtcDestroyProgram(&prog);
-    throw std::runtime_error("hiprtc compile failed:\n" + log.substr(0, 4000));
-  }
-  size_t cs = 0;
-  hiprtcGetCodeSize(prog, &cs);
-  std::vector<char> code(cs);
-  hiprtcGetCode(prog, code.data());
-  hiprtcDestroyProgram(&prog);
-  return code;
-}
-
+// ------------------------------------------------------------------------------ compile + cache (jit_util.h)
 struct JitEntry {
   std::vector<char> code;
   hipModule_t mod = nullptr;
@@ -494,11 +457,6 @@ struct JitEntry {
 static std::mutex g_mu;
 static std::vector<std::unique_ptr<JitEntry>> g_entries;
 static std::unordered_map<std::string, int> g_by_key;
-
-static bool file_exists(const std::string& p) {
-  struct stat st;
-  return stat(p.c_str(), &st) == 0;
-}
 
 // Generate + compile (or load from the disk cache) pass p; returns a handle.  No GPU needed.
 int jit_prepare(const std::vector<int>& blob, int p, bool adjoint, const std::string& cache_dir,
@@ -515,7 +473,7 @@ int jit_prepare(const std::vector<int>& blob, int p, bool adjoint, const std::st
     ss2 << f2.rdbuf();
     header += ss2.str();
   }
-  const std::string key = hex64(fnv1a(spec.source + header + arch));
+  const std::string key = hex64(fnv1a(spec.source + header + arch + hiprtc_version_tag()));
   if (key_out) *key_out = key;
   std::lock_guard<std::mutex> lk(g_mu);
   auto it = g_by_key.find(key);
@@ -527,34 +485,10 @@ int jit_prepare(const std::vector<int>& blob, int p, bool adjoint, const std::st
   e->n = spec.n;
   e->bf16 = bf16;
   e->key = key;
-  const std::string path = cache_dir + "/" + key + ".co";
-  if (!cache_dir.empty() && file_exists(path)) {
-    std::ifstream f(path, std::ios::binary);
-    e->code.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
-  }
+  e->code = cache_load(cache_dir, key);
   if (e->code.empty()) {
     e->code = hiprtc_compile(spec.source, include_dir, arch);
-    if (!cache_dir.empty()) {
-      mkdir(cache_dir.c_str(), 0755);
-      // one temp file per process: the ranks of a node share the cache and may compile the same key at once;
-      // each renames a complete file of its own over the entry, so a reader never sees a partial code object
-      const std::string tag = "." + std::to_string((long)getpid()) + ".tmp";
-      std::string tmp = path + tag;
-      bool ok;
-      {
-        std::ofstream f(tmp, std::ios::binary);
-        f.write(e->code.data(), (std::streamsize)e->code.size());
-        ok = (bool)f;
-      }
-      if (ok) std::rename(tmp.c_str(), path.c_str());
-      else std::remove(tmp.c_str());
-      const std::string src = cache_dir + "/" + key + ".hip";
-      {
-        std::ofstream fs(src + tag);
-        fs << spec.source;
-      }
-      std::rename((src + tag).c_str(), src.c_str());
-    }
+    cache_store(cache_dir, key, e->code, spec.source);
   }
   g_entries.push_back(std::move(e));
   int h = (int)g_entries.size() - 1;

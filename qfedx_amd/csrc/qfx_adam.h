@@ -2,8 +2,10 @@
 // (csrc/train_kernels.hip) and the Adam epilogue of hea_grad_reduce_kernel (csrc/hea_mfma.hip), so the fused and
 // the separate launch produce bitwise the same parameters.
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
 #include <math.h>
+#endif
 
 #include "hea_args.h"   // QfxAdamArgs
 

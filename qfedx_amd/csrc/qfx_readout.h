@@ -2,7 +2,9 @@
 // engine's first adjoint pass, which computes its sample's dL/d<Z> itself (hea_mfma.hip, fused readout): both paths
 // run the same operations in the same order, so they give the same values.
 #pragma once
+#ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
+#endif
 
 namespace qfx_ro {
 

@@ -121,7 +121,8 @@ class VQCEngine:
         if samples * hip.tiles_last >= 2 * cus:
             return False
         from .hea_mfma import HeaMfmaProgram
-        small = HeaMfmaProgram(self.spec, self.device, tile_bits=13, storage=hip.storage)
+        small = HeaMfmaProgram(self.spec, self.device, tile_bits=13, storage=hip.storage,
+                               use_spec=hip.spec_requested)   # (compiles its per-plan kernels now: no graph exists yet)
         if small.n_passes != hip.n_passes:
             return False
         small.fused_readout = hip.fused_readout

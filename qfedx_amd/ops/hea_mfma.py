@@ -57,6 +57,18 @@ def _frag_index(ops: np.ndarray) -> torch.Tensor:
         elif code == OP_BACK2:
             out[i, 1] = 4 * int(w[W_SLOT2]) + 2
     return torch.from_numpy(out).contiguous()
+
+
+def spec_default() -> bool:
+    """Per-plan pass kernels (csrc/hea_spec.cpp) instead of the interpreter: on by default, ``QFEDX_HEA_SPEC=0`` selects
+    the interpreter (docs/ARCHITECTURE.md section 1b).  ``QFEDX_DEBUG=1`` stays on the interpreter: the device checks
+    validate the op records the per-plan build no longer reads."""
+    if os.environ.get("QFEDX_DEBUG", "0") == "1":
+        return False
+    return os.environ.get("QFEDX_HEA_SPEC", "1") != "0"
+
+
+_SPEC_WARNED = False
 _NO_KEYS = torch.zeros(0, dtype=torch.int64)
 _NODBG = torch.zeros(0, dtype=torch.int64)     # no stall-attribution buffer (stamps build only)
 
@@ -67,7 +79,7 @@ FUSED_ADAM_MAX_BLOCKS = 256   # hea_grad_reduce blocks (clients x gradient ops) 
 
 class HeaMfmaProgram:
     def __init__(self, spec, device, tile_bits: int | None = None, adj_tile_bits: int | None = None,
-                 storage: str = "fp16"):
+                 storage: str = "fp16", use_spec: bool | None = None):
         """``storage``: fp16 (default) or bf16 (BASELINE config 2) amplitudes and unitary fragments
         (csrc/hea_mfma_bf16.hip: v_mfma_f32_16x16x32_bf16, fp32 accumulation; 2^-9 per-op state rounding)."""
         if storage not in ("fp16", "bf16"):
@@ -129,6 +141,7 @@ class HeaMfmaProgram:
             progs_f = [(p, f if j < self.fwd_last else (fr_ops if j == self.fwd_last else f[:0]), a)
                        for j, (p, f, a) in enumerate(progs_f)]
         self.n_regions = []       # per pass: gradient records of its adjoint program (LDS regions)
+        self._host_progs = []     # per pass: host (ops, fidx) of the forward / adjoint programs (per-plan kernels)
         for (p, fwd, _), (pa, _, adj) in zip(progs_f, progs_a):
             f = torch.from_numpy(fwd.astype(np.int32)).contiguous()
             a = torch.from_numpy(adj.astype(np.int32)).contiguous()
@@ -141,6 +154,7 @@ class HeaMfmaProgram:
             oa = torch.from_numpy(fo_table(adj, pa, self.n).reshape(-1)).to(self.device)
             self.passes.append((p, (f.to(self.device), ff.to(self.device), of),
                                 (a.to(self.device), fa.to(self.device), oa), pa))
+            self._host_progs.append(((f, ff), (a, fa)))
         slot_tab = np.zeros((max(self.n_slots, 1), 9), dtype=np.int32)
         owner = np.zeros(self.n_theta, dtype=np.int32)
         for p in self.plan.passes:
@@ -168,6 +182,91 @@ class HeaMfmaProgram:
         self.fused_readout = True
         if self.device.type == "cuda":
             self._shift_budget()      # query free HBM now, never inside a graph capture
+        # per-plan pass kernels: compiled (or loaded from the cache) and their modules loaded here, never inside a
+        # stream capture
+        self.spec_fwd = [-1] * len(self.passes)
+        self.spec_adj = [-1] * len(self.passes)
+        self.spec_keys = []
+        self.spec_launches = 0      # pass launches that ran a per-plan kernel / the interpreter (tests, tools)
+        self.interp_launches = 0
+        self.spec_requested = spec_default() if use_spec is None else bool(use_spec)
+        if self.spec_requested:
+            self.prepare_spec()
+
+    @property
+    def spec_active(self) -> bool:
+        """At least one pass of this program has a per-plan kernel.  Which passes a step launches per plan:
+        ``spec_passes``; how many launches actually did: ``spec_launches`` / ``interp_launches``."""
+        return any(h >= 0 for h in self.spec_fwd + self.spec_adj)
+
+    def spec_passes(self, fused_readout: bool | None = None) -> dict:
+        """Per pass, whether a training step launches its per-plan kernel (True) or the interpreter: forward passes
+        0..fwd_last and adjoint passes 0..J-1.  ``fused_readout`` (default: what a noiseless step does): the last
+        adjoint pass then runs on the interpreter."""
+        fused = self._fused_readout(None) if fused_readout is None else fused_readout
+        J = self.n_passes
+        return {"fwd": [self.spec_fwd[j] >= 0 for j in range(self.fwd_last + 1)],
+                "adj": [self._adj_handle(j, fused and j == J - 1) >= 0 for j in range(J)]}
+
+    def _adj_handle(self, j: int, computes_readout: bool) -> int:
+        """Kernel of adjoint pass j: the pass that computes the fused readout runs on the interpreter.  Compiled per
+        plan, its cross entropy (expf / logf and fp32 sums of one thread per workgroup) gave dL/d<Z> different in the
+        last bit for a share of the samples, and the paths must agree bitwise (with the readout kernel too:
+        tests/test_gpu_hea.py).  Without the fused readout the same pass runs its per-plan kernel."""
+        return -1 if computes_readout else self.spec_adj[j]
+
+    def _count(self, handle: int) -> int:
+        if handle >= 0:
+            self.spec_launches += 1
+        else:
+            self.interp_launches += 1
+        return handle
+
+    def spec_cfg(self, j: int, adjoint: bool) -> list:
+        """Constants pass j's per-plan kernel is compiled with (hea_bindings.cpp spec_desc)."""
+        p = self.passes[j][3] if adjoint else self.passes[j][0]
+        J = self.n_passes
+        gen, load_lam, store_lam = (0, int(j < J - 1), int(j > 0)) if adjoint else (int(j == 0), 0, 0)
+        glo = os.environ.get("QFEDX_EXTRA_HIPFLAGS", "")
+        gate_lo = 0 if "-DQFX_HEA_GATE_LO=0" in glo else (1 if "-DQFX_HEA_GATE_LO=1" in glo else -1)
+        from .. import _build
+        return [self.n, p.t, p.c, p.lo, p.hi, self.C, gen, load_lam, store_lam,
+                self.n_regions[j] if adjoint else 0] + [int(h) for h in p.H] + \
+               [int(self.bf16), int(_build.variant() == "stamps"), gate_lo]
+
+    def prepare_spec(self) -> bool:
+        """Compile (or load from ``QFEDX_JIT_CACHE``) the forward and adjoint kernel of every pass; on a failure warn
+        once and stay on the interpreter."""
+        global _SPEC_WARNED
+        from .statevec_hip import ARCH, CSRC, JIT_CACHE
+        JIT_CACHE = os.environ.get("QFEDX_JIT_CACHE", JIT_CACHE)     # (read per call: tests point it at a tmp dir)
+        C = ext()
+        fwd, adj, keys = [-1] * self.n_passes, [-1] * self.n_passes, []
+        try:
+            for j, ((f, ff), (a, fa)) in enumerate(self._host_progs):
+                # The forward pass that generates the layer-1 product state stays on the interpreter: compiled per
+                # plan, its fp32 complex products came out different in the last bit on a share of the amplitudes (FMA
+                # contraction follows the surrounding code), and the two paths must agree bitwise.
+                if 0 < j <= self.fwd_last and len(f):
+                    fwd[j], k = C.hea_spec_prepare(False, f, ff, self.spec_cfg(j, False), JIT_CACHE, CSRC, ARCH)
+                    keys.append(k)
+                if len(a):
+                    adj[j], k = C.hea_spec_prepare(True, a, fa, self.spec_cfg(j, True), JIT_CACHE, CSRC, ARCH)
+                    keys.append(k)
+            if self.device.type == "cuda":
+                with torch.cuda.device(self.device):     # (a module is loaded on the device it is launched on)
+                    for h in fwd + adj:
+                        if h >= 0:
+                            C.hea_spec_load(h)
+        except RuntimeError as e:
+            if not _SPEC_WARNED:
+                import warnings
+                warnings.warn(f"per-plan MFMA pass kernels unavailable, using the interpreter: {e}")
+                _SPEC_WARNED = True
+            self.spec_fwd, self.spec_adj, self.spec_keys = [-1] * self.n_passes, [-1] * self.n_passes, []
+            return False
+        self.spec_fwd, self.spec_adj, self.spec_keys = fwd, adj, keys
+        return True
 
     # ------------------------------------------------------------------ workspaces
     @contextlib.contextmanager
@@ -248,7 +347,8 @@ class HeaMfmaProgram:
             psi_in = stored[-1] if j > 0 else empty
             geom = self._geom(p, j == 0, False, keep, False, B, params.shape[1], S, x.shape[1], K, shared=shared)
             C.hea_pass(False, fwd[0], fwd[1], fwd[2], geom, self.scale, psi_in, out, empty, empty, x, params, fr, fempty,
-                       part if j == R else fempty, fempty, dbg[f"fwd{j}"] if dbg else _NODBG)
+                       part if j == R else fempty, fempty, dbg[f"fwd{j}"] if dbg else _NODBG,
+                       spec=self._count(self.spec_fwd[j]))
             if keep:
                 stored.append(out)
         if store_last:
@@ -276,10 +376,12 @@ class HeaMfmaProgram:
                 part, yy, ww, expz, rec = readout
                 C.hea_pass(True, adj[0], adj[1], adj[2], geom, self.scale, stored[j], empty, lam_in, lam_out, x,
                            params, fr, fempty, part, gslab, dbg[f"adj{j}"] if dbg else _NODBG,
-                           [yy, ww, expz, wread, rec], self.tiles_last)
+                           [yy, ww, expz, wread, rec], self.tiles_last,
+                           spec=self._count(self._adj_handle(j, True)))
             else:
                 C.hea_pass(True, adj[0], adj[1], adj[2], geom, self.scale, stored[j], empty, lam_in, lam_out, x,
-                           params, fr, wread, fempty, gslab, dbg[f"adj{j}"] if dbg else _NODBG)
+                           params, fr, wread, fempty, gslab, dbg[f"adj{j}"] if dbg else _NODBG,
+                           spec=self._count(self._adj_handle(j, False)))
             lam_in = lam_out
 
     def _prep(self, xang, params):
@@ -509,7 +611,8 @@ class HeaMfmaProgram:
             first = jj == j
             geom = self._geom(p, jj == 0, False, keep, False, B, ps, S, xs.shape[1], Kr, nr if first else 1)
             E.hea_pass(False, fwd[0], fwd[1], fwd[2], geom, self.scale, psi_in, out, empty, empty, xs, thr, fr, fempty,
-                       part if jj == R else fempty, fempty, _NODBG)
+                       part if jj == R else fempty, fempty, _NODBG,
+                       spec=self._count(self.spec_fwd[jj]))
             psi_in = out
         z = self._buf("pbz", S * self.C, torch.float32)
         E.readout_sum(part, self.tiles_last, self.C, S, z)

@@ -20,6 +20,8 @@ def main():
     ap.add_argument("--clients", type=int, default=64)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--spec", type=int, choices=(0, 1), default=None,
+                    help="1: per-plan pass kernels, 0: the interpreter (default: QFEDX_HEA_SPEC)")
     ap.add_argument("--precision", action="store_true", help="also report errors against the fp32 VALU engine")
     args = ap.parse_args()
     import torch
@@ -29,7 +31,8 @@ def main():
 
     dev = torch.device("cuda", 0)
     spec = VQCSpec(args.qubits, args.layers, 3)
-    prog = HeaMfmaProgram(spec, dev)
+    prog = HeaMfmaProgram(spec, dev, use_spec=None if args.spec is None else bool(args.spec))
+    sf, sa = getattr(prog, "spec_fwd", None), getattr(prog, "spec_adj", None)   # (older trees: no per-plan kernels)
     K, B = args.clients, args.batch
     S = K * B
     g = torch.Generator().manual_seed(0)
@@ -60,7 +63,10 @@ def main():
     fempty = torch.empty(0, dtype=torch.float32, device=dev)
     J = prog.n_passes
     N = S << prog.n
-    res = {"step_ms": round(step_ms, 4), "n_passes": J, "samples": S}
+    res = {"step_ms": round(step_ms, 4), "n_passes": J, "samples": S, "spec": bool(getattr(prog, "spec_active", False)),
+           # per pass: does a training step launch the per-plan kernel (the timed step_ms) - the per-pass lines below
+           # launch a pass's per-plan kernel whenever it has one
+           "spec_passes": prog.spec_passes() if hasattr(prog, "spec_passes") else None}
 
     def timeit(fn, name, nbytes):
         fn()
@@ -85,7 +91,8 @@ def main():
         geom = prog._geom(p, j == 0, False, True, False, B, params.shape[1], S, xx.shape[1], K)
         nb = 4 * N * ((j > 0) + 1)
         timeit(lambda: C.hea_pass(False, fwd[0], fwd[1], fwd[2], geom, prog.scale, psi_in, out, empty, empty, xx, params, fr, fempty,
-                                  part if j == R else fempty, fempty, _NODBG), f"fwd{j}", nb)
+                                  part if j == R else fempty, fempty, _NODBG, **({"spec": sf[j]} if sf else {})),
+               f"fwd{j}", nb)
     lam = [prog._buf("lam0", N, torch.int32), prog._buf("lam1", N, torch.int32)]
     for j in range(J - 1, -1, -1):
         ent = prog.passes[j]                          # (fwd pass, fwd prog, adj prog[, adj pass]) (older trees: 3)
@@ -96,7 +103,8 @@ def main():
         lout = lam[j % 2] if j > 0 else empty
         nb = 4 * N * (1 + (j < J - 1) + (j > 0))
         timeit(lambda: C.hea_pass(True, adj[0], adj[1], adj[2], geom, prog.scale, stored[j], empty, lin, lout,
-                                  xx, params, fr, wread, fempty, gslab, _NODBG), f"adj{j}", nb)
+                                  xx, params, fr, wread, fempty, gslab, _NODBG, **({"spec": sa[j]} if sa else {})),
+               f"adj{j}", nb)
     grad = torch.zeros(K, params.shape[1], device=dev)
     timeit(lambda: C.hea_grad_reduce(gslab, prog.slab_tiles, prog.n_gradops, prog.gmeta, B, K, params, grad,
                                      params.shape[1]), "grad_reduce", 0)

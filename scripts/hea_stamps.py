@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--clients", type=int, default=64)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--out", default="")
+    ap.add_argument("--spec", type=int, choices=(0, 1), default=None,
+                    help="1: per-plan pass kernels (compiled with the stamps), 0: the interpreter (default: QFEDX_HEA_SPEC)")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -49,7 +51,8 @@ def main():
     y = torch.randint(0, 3, (K, B), generator=g).to(dev)
     w = torch.full((K, B), 1.0 / B, device=dev)
     params = torch.stack([spec.init_params(k) for k in range(K)]).to(dev)
-    prog = HeaMfmaProgram(spec, dev)
+    prog = HeaMfmaProgram(spec, dev, use_spec=None if args.spec is None else bool(args.spec))
+    print(json.dumps({"spec": prog.spec_active, "spec_passes": prog.spec_passes()}), flush=True)
     for _ in range(3):                                  # warm caches / clocks
         prog.loss_and_grads(x, y, w, params, spec)
     dbg = prog.stamp_buffers()

@@ -1,6 +1,6 @@
 """Per-basic-block instruction mix of one kernel in a hipcc --save-temps .s file (gfx950).
 
-python tools/isa_blocks.py FILE.s KERNEL_SUBSTRING [--min N]
+python tools/isa_blocks.py FILE.s KERNEL_SUBSTRING [--min N]   (mangled kernels, or the extern "C" qfx_* ones)
 Prints, per block: label, source line, VALU / SALU / LDS / MFMA / VMEM counts and the block's loop annotation, so
 the static cost of each region (group op, epilogue, setup) can be read off and multiplied by its dynamic count.
 """
@@ -10,8 +10,8 @@ import sys
 
 def kernel_lines(path, sub):
     lines = open(path).read().split("\n")
-    start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\S*:", l) and sub in l)
-    end = next((i for i in range(start + 1, len(lines)) if re.match(r"^_Z\S*:", lines[i])), len(lines))
+    start = next(i for i, l in enumerate(lines) if re.match(r"^(_Z|qfx_)\S*:", l) and sub in l)
+    end = next((i for i in range(start + 1, len(lines)) if re.match(r"^(_Z|qfx_)\S*:", lines[i])), len(lines))
     return lines[start:end]
 
 
