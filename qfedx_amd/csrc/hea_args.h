@@ -48,6 +48,8 @@ struct HeaPassArgs {
   // dL/d<Z> from the readout partials (part, ro_tps tiles) instead of reading wread; the tile-0 workgroup writes
   // ro_expz / ro_w [S][C] (the later passes' wread) and the per-sample reduction record ro_rec [S][2C + 2]
   // (dl_c z_c, dl_c, loss term, hit) that hea_grad_reduce sums per client.
+  // A split-readout step leaves ro_fuse = 0: hea_readout_rec_kernel (hea_step.hip) writes the same ro_expz / ro_w /
+  // ro_rec values once per sample before the adjoint passes, and this pass reads ro_w as its wread.
   int ro_fuse, ro_tps;
   const long long* ro_y;
   const float* ro_wts;

@@ -21,6 +21,9 @@ int qfx_hea_frags(const float* params, int p_stride, const int* slot_tab, int n_
 int qfx_hea_grad_reduce(const long long* gslab, int slab_tiles, int n_gradops, const int* gmeta, int spc, int K,
                         float* params, float* grad, int p_stride, const QfxAdamArgs* adam,
                         const QfxReadoutRed* readout, const QfxFedTail* fed, hipStream_t st);
+int qfx_hea_readout_rec(const float* part, int tps, int C, int spc, int K, const long long* y, const float* wts,
+                        const float* params, int p_stride, int n_theta, float* expz, float* wread, float* rec,
+                        hipStream_t st);
 int qfx_hea_args_size();
 int qfx_hea_check_status(hipStream_t st);
 // bf16 state storage (hea_mfma_bf16.hip)
@@ -233,6 +236,25 @@ void hea_frags(torch::Tensor params, int64_t p_stride, torch::Tensor slot_tab, i
         "qfx_hea_frags");
 }
 
+// Split-readout step: every sample's <Z> (expz [S, C]), readout weights (wread [S, C]: the adjoint passes' input) and
+// reduction record (rec [S, 2C + 2]) from the readout pass's partials (part [S, tps, C]), ahead of the adjoint passes
+// (hea_readout_rec_kernel: bitwise what the fused readout pass writes).
+void hea_readout_rec(torch::Tensor part, int64_t tps, int64_t C, int64_t spc, int64_t K, torch::Tensor y,
+                     torch::Tensor wts, torch::Tensor params, int64_t n_theta, torch::Tensor expz, torch::Tensor wread,
+                     torch::Tensor rec) {
+  const int64_t S = K * spc;
+  need(C >= 1 && C <= 8 && tps >= 1 && spc >= 1 && K >= 0, "readout_rec: 1..8 classes, >= 1 tile and sample per client");
+  need(params.dim() == 2 && params.size(0) >= K, "readout_rec: params must be [K, p_stride]");
+  const int64_t p_stride = params.size(1);
+  need(n_theta >= 0 && n_theta + 2 * C <= p_stride, "readout_rec: readout parameters past the parameter row");
+  check(qfx_hea_readout_rec(dp<float>(part, torch::kFloat32, "part", S * tps * C), (int)tps, (int)C, (int)spc, (int)K,
+                            dp<long long>(y, torch::kInt64, "y", S), dp<float>(wts, torch::kFloat32, "wts", S),
+                            dp<float>(params, torch::kFloat32, "params", K * p_stride), (int)p_stride, (int)n_theta,
+                            dp<float>(expz, torch::kFloat32, "expz", S * C), dp<float>(wread, torch::kFloat32, "wread", S * C),
+                            dp<float>(rec, torch::kFloat32, "rec", S * (2 * C + 2)), cur()),
+        "qfx_hea_readout_rec");
+}
+
 // adam: optional (m, v, t_in, t_out, active, cnt) device tensors [K, P] / [K] (cnt int32, zero-initialised) and
 // lr, b1, b2, eps: the clients' Adam step fused into the reduction (the last block of each client updates its row)
 // readout: optional (rec [K * spc, 2C + 2], loss [K], correct [K]) of a fused-readout step and ro_c = C, ro_ntheta:
@@ -359,6 +381,9 @@ void register_hea(pybind11::module& m) {
   m.def("hea_frags", &hea_frags, pybind11::arg("params"), pybind11::arg("p_stride"), pybind11::arg("slot_tab"),
         pybind11::arg("n_slots"), pybind11::arg("K"), pybind11::arg("frags"), pybind11::arg("bf16") = false);
   m.def("hea_check_ops", &hea_check_ops);
+  m.def("hea_readout_rec", &hea_readout_rec, pybind11::arg("part"), pybind11::arg("tps"), pybind11::arg("C"),
+        pybind11::arg("spc"), pybind11::arg("K"), pybind11::arg("y"), pybind11::arg("wts"), pybind11::arg("params"),
+        pybind11::arg("n_theta"), pybind11::arg("expz"), pybind11::arg("wread"), pybind11::arg("rec"));
   m.def("hea_grad_reduce", &hea_grad_reduce, pybind11::arg("gslab"), pybind11::arg("slab_tiles"),
         pybind11::arg("n_gradops"), pybind11::arg("gmeta"), pybind11::arg("spc"), pybind11::arg("K"),
         pybind11::arg("params"), pybind11::arg("grad"), pybind11::arg("p_stride"),

@@ -169,6 +169,56 @@ __global__ void __launch_bounds__(256) hea_grad_reduce_kernel(const long long* _
   for (long e = tid; e < (long)p_stride + 6 + ft.n_norms; e += 256)
     qfx::round_apply_elem(ft.buf, p_stride, ft.apply_theta, 1.0, ft.apply_out, 0, 1.0, ft.n_norms, e, wsum, ld);
 }
+
+// Per-sample readout record of a split-readout step (HeaMfmaProgram._step): what the tile-0 workgroup of the fused
+// readout pass writes (hea_mfma.hip, a.ro_fuse), computed once per sample ahead of the adjoint passes, so the last
+// adjoint pass reads wread like the others and runs its per-plan kernel.  One thread per sample; the same operations
+// in the same order as the fused block (tile sums from 0.f in tile order, qfx_ro::ce_sample), so every value is
+// bitwise the fused step's.  Every per-class array is indexed by unrolled constants (nothing in scratch).
+__global__ void __launch_bounds__(64) hea_readout_rec_kernel(const float* __restrict__ part, int tps, int C, int spc,
+                                                             long S, const long long* __restrict__ y,
+                                                             const float* __restrict__ wts,
+                                                             const float* __restrict__ params, int p_stride,
+                                                             int n_theta, float* __restrict__ expz,
+                                                             float* __restrict__ wread, float* __restrict__ rec_out) {
+  const long s = (long)blockIdx.x * 64 + threadIdx.x;
+  if (s >= S) return;
+  const float* prm = params + (size_t)(s / spc) * p_stride + n_theta;
+  const float* base = part + (size_t)s * tps * C;
+  float z[qfx_ro::RO_CMAX], ra[2 * qfx_ro::RO_CMAX], rb[qfx_ro::RO_CMAX], dl[qfx_ro::RO_CMAX], lterm, hit;
+#pragma unroll
+  for (int c = 0; c < 2 * qfx_ro::RO_CMAX; ++c) ra[c] = c < 2 * C ? prm[c] : 0.f;
+#pragma unroll
+  for (int c = 0; c < qfx_ro::RO_CMAX; ++c) rb[c] = c < C ? prm[C + c] : 0.f;
+  const float ws = wts[s];
+  const int yy = (int)y[s];
+#pragma unroll
+  for (int c = 0; c < qfx_ro::RO_CMAX; ++c) z[c] = 0.f;
+  for (int u0 = 0; u0 < tps; u0 += 8) {   // 8 tiles' loads in flight, added in tile order
+    float v[8][qfx_ro::RO_CMAX];
+#pragma unroll
+    for (int du = 0; du < 8; ++du)
+#pragma unroll
+      for (int c = 0; c < qfx_ro::RO_CMAX; ++c) v[du][c] = (u0 + du < tps && c < C) ? base[(size_t)(u0 + du) * C + c] : 0.f;
+#pragma unroll
+    for (int du = 0; du < 8; ++du)
+#pragma unroll
+      for (int c = 0; c < qfx_ro::RO_CMAX; ++c)
+        if (u0 + du < tps && c < C) z[c] += v[du][c];
+  }
+  qfx_ro::ce_sample(z, ra, rb, C, yy, ws, dl, lterm, hit);
+  float* rec = rec_out + (size_t)s * (2 * C + 2);
+#pragma unroll
+  for (int c = 0; c < qfx_ro::RO_CMAX; ++c) {
+    if (c >= C) break;
+    expz[(size_t)s * C + c] = z[c];
+    wread[(size_t)s * C + c] = dl[c] * ra[c];
+    rec[c] = dl[c] * z[c];
+    rec[C + c] = dl[c];
+  }
+  rec[2 * C] = lterm;
+  rec[2 * C + 1] = hit;
+}
 #endif  // !QFX_HEA_BF16
 
 }  // namespace HEA_NS
@@ -199,6 +249,17 @@ extern "C" int qfx_hea_grad_reduce(const long long* gslab, int slab_tiles, int n
   }
   hipLaunchKernelGGL(HEA_NS::hea_grad_reduce_kernel, dim3(K, rows), dim3(256), 0, st, gslab, slab_tiles, n_gradops,
                      gmeta, spc, params, grad, p_stride, ad, ro, ftl);
+  return (int)hipGetLastError();
+}
+
+extern "C" int qfx_hea_readout_rec(const float* part, int tps, int C, int spc, int K, const long long* y,
+                                   const float* wts, const float* params, int p_stride, int n_theta, float* expz,
+                                   float* wread, float* rec, hipStream_t st) {
+  const long S = (long)K * spc;
+  if (S == 0) return 0;
+  if (C < 1 || C > qfx_ro::RO_CMAX || tps < 1 || n_theta + 2 * C > p_stride) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(HEA_NS::hea_readout_rec_kernel, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, part, tps, C,
+                     spc, S, y, wts, params, p_stride, n_theta, expz, wread, rec);
   return (int)hipGetLastError();
 }
 

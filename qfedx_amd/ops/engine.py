@@ -126,6 +126,7 @@ class VQCEngine:
         if small.n_passes != hip.n_passes:
             return False
         small.fused_readout = hip.fused_readout
+        small.split_readout = hip.split_readout
         self.hip = small
         return True
 

@@ -5,7 +5,8 @@
 
     hea_frags (per-client 16 x 16 group unitaries -> MFMA A fragments, hi + lo fp16)
     forward passes  (product state generated in-tile; intermediate pass outputs stored as fp16 (re, im))
-    readout_ce      (shared with the VALU engine: <Z>, CE loss, dL/d<Z>, a/b gradients)
+    readout_ce      (shared with the VALU engine: <Z>, CE loss, dL/d<Z>, a/b gradients; noiseless steps instead
+                     compute them per sample in hea_readout_rec or inside the last adjoint pass: ``readout_mode``)
     adjoint passes  (reverse pass order; per-workgroup gradient partials)
     hea_grad_reduce (fixed-order sum over each client's samples and tiles)
 
@@ -68,6 +69,14 @@ def spec_default() -> bool:
     return os.environ.get("QFEDX_HEA_SPEC", "1") != "0"
 
 
+def split_readout_default():
+    """``QFEDX_HEA_SPLIT_RO`` = 1 / 0 forces the split-readout step on / off wherever it is possible
+    (``HeaMfmaProgram.readout_mode``); unset (None): by sample count, ``SPLIT_READOUT_MIN_SAMPLES``.  ``0`` makes every
+    step launch what it launched before the split route existed."""
+    env = os.environ.get("QFEDX_HEA_SPLIT_RO", "")
+    return None if env == "" else env != "0"
+
+
 _SPEC_WARNED = False
 _NO_KEYS = torch.zeros(0, dtype=torch.int64)
 _NODBG = torch.zeros(0, dtype=torch.int64)     # no stall-attribution buffer (stamps build only)
@@ -75,6 +84,12 @@ _NODBG = torch.zeros(0, dtype=torch.int64)     # no stall-attribution buffer (st
 
 NT_STORE_MIN_BYTES = 128 << 20   # pass states above which tiles are stored non-temporally (_nt_store)
 FUSED_ADAM_MAX_BLOCKS = 256   # hea_grad_reduce blocks (clients x gradient ops) up to which Adam is fused
+# Samples per step (clients x batch) from which a noiseless step computes the readout records in a launch of their own
+# and runs the last adjoint pass per plan (readout_mode).  Measured, 16q x 3L, clients x 32 samples, ms per round fused
+# -> split: 32 samples 0.090 -> 0.089 and 64 samples 0.111 -> 0.109 (inside 3 x the run-to-run spread), 128 samples
+# 0.166 -> 0.159, 256 0.270 -> 0.253, 512 0.480 -> 0.444, 2048 1.659 -> 1.509 (profiles/split_readout_ab.txt).  Never
+# below 64: steps of a few samples stay fused whatever a box measures.
+SPLIT_READOUT_MIN_SAMPLES = 128
 
 
 class HeaMfmaProgram:
@@ -178,7 +193,8 @@ class HeaMfmaProgram:
         self._ws = {}
         self._ps_budget = None
         # noiseless steps compute the readout in the first adjoint pass (profiles/r5_fused_readout_ab.txt: a tie at 64
-        # clients, -2.7% at 8); the readout kernel runs for readout noise - and for tests comparing the two (False)
+        # clients, -2.7% at 8); the readout kernel runs for readout noise - and for tests comparing the two (False).
+        # Larger steps compute the same values in a launch of their own ahead of the adjoint (readout_mode: split).
         self.fused_readout = True
         if self.device.type == "cuda":
             self._shift_budget()      # query free HBM now, never inside a graph capture
@@ -190,6 +206,8 @@ class HeaMfmaProgram:
         self.spec_launches = 0      # pass launches that ran a per-plan kernel / the interpreter (tests, tools)
         self.interp_launches = 0
         self.spec_requested = spec_default() if use_spec is None else bool(use_spec)
+        # split-readout steps (readout_mode): None = by sample count, True / False = wherever possible / never
+        self.split_readout = split_readout_default()
         if self.spec_requested:
             self.prepare_spec()
 
@@ -199,11 +217,31 @@ class HeaMfmaProgram:
         ``spec_passes``; how many launches actually did: ``spec_launches`` / ``interp_launches``."""
         return any(h >= 0 for h in self.spec_fwd + self.spec_adj)
 
-    def spec_passes(self, fused_readout: bool | None = None) -> dict:
+    def readout_mode(self, samples: int | None = None, noise=None) -> str:
+        """How a training step of ``samples`` samples (clients x batch) computes its readout:
+
+        ``kernel``  the readout / cross-entropy kernel (readout noise, ``fused_readout`` off, > 64 partials per sample)
+        ``fused``   inside the last adjoint pass, which therefore runs on the interpreter (``_adj_handle``)
+        ``split``   ``hea_readout_rec`` writes every sample's <Z>, dL/d<Z> and reduction record once, bitwise what the
+                    fused pass writes, and the last adjoint pass runs its per-plan kernel: chosen among the steps that
+                    would fuse when that pass has a per-plan kernel and ``samples >= SPLIT_READOUT_MIN_SAMPLES``
+                    (``split_readout`` = True / False replaces the sample-count rule).
+        Without a sample count: ``fused`` or ``kernel``, the meaning ``spec_passes()`` always had."""
+        if not self._fused_readout(noise):
+            return "kernel"
+        if samples is None or not self.spec_adj or self.spec_adj[-1] < 0:
+            return "fused"
+        split = samples >= SPLIT_READOUT_MIN_SAMPLES if self.split_readout is None else self.split_readout
+        return "split" if split else "fused"
+
+    def spec_passes(self, fused_readout: bool | None = None, samples: int | None = None) -> dict:
         """Per pass, whether a training step launches its per-plan kernel (True) or the interpreter: forward passes
         0..fwd_last and adjoint passes 0..J-1.  ``fused_readout`` (default: what a noiseless step does): the last
-        adjoint pass then runs on the interpreter."""
+        adjoint pass then runs on the interpreter - unless the step has ``samples`` samples and takes the split route
+        (``readout_mode``)."""
         fused = self._fused_readout(None) if fused_readout is None else fused_readout
+        if fused and samples is not None and self.readout_mode(samples) == "split":
+            fused = False
         J = self.n_passes
         return {"fwd": [self.spec_fwd[j] >= 0 for j in range(self.fwd_last + 1)],
                 "adj": [self._adj_handle(j, fused and j == J - 1) >= 0 for j in range(J)]}
@@ -650,12 +688,20 @@ class HeaMfmaProgram:
         # Fused readout: the first adjoint pass computes each sample's <Z>, cross entropy and dL/d<Z> from the readout
         # partials, and the gradient reduction sums the clients' loss, hits and readout gradients - one launch fewer
         # per local step.
+        # Split readout (readout_mode): those per-sample values come from a launch of their own, once per sample instead of
+        # once per adjoint tile, and the last adjoint pass - no longer the one that computes them - runs per plan.  The
+        # records and the reduction are the fused route's, bit for bit.
         ro = None
-        if self._fused_readout(noise):
+        mode = self.readout_mode(S, noise)
+        if mode != "kernel":
             rec = self._buf("rorec", S * (2 * self.C + 2), torch.float32)
             ro = [rec, loss, correct]
-            self._adjoint(x, p, fr, K, B, stored, wread, gslab, readout=(part, yy, ww, expz, rec), dbg=dbg,
-                          shared=shared)
+            if mode == "split":
+                C.hea_readout_rec(part, self.tiles_last, self.C, B, K, yy, ww, p, self.n_theta, expz, wread, rec)
+                self._adjoint(x, p, fr, K, B, stored, wread, gslab, dbg=dbg, shared=shared)
+            else:
+                self._adjoint(x, p, fr, K, B, stored, wread, gslab, readout=(part, yy, ww, expz, rec), dbg=dbg,
+                              shared=shared)
         else:
             if noise is None:
                 C.readout_ce(part, self.tiles_last, self.C, B, K, yy, ww, p, self.n_theta, expz, wread, loss,

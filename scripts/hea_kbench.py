@@ -66,7 +66,10 @@ def main():
     res = {"step_ms": round(step_ms, 4), "n_passes": J, "samples": S, "spec": bool(getattr(prog, "spec_active", False)),
            # per pass: does a training step launch the per-plan kernel (the timed step_ms) - the per-pass lines below
            # launch a pass's per-plan kernel whenever it has one
-           "spec_passes": prog.spec_passes() if hasattr(prog, "spec_passes") else None}
+           "spec_passes": (prog.spec_passes(samples=S) if hasattr(prog, "readout_mode") else
+                           prog.spec_passes() if hasattr(prog, "spec_passes") else None),
+           # (fused: the last adjoint pass computes the readout, on the interpreter; split: hea_readout_rec + per plan)
+           "readout_mode": prog.readout_mode(S) if hasattr(prog, "readout_mode") else None}
 
     def timeit(fn, name, nbytes):
         fn()

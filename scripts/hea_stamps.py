@@ -52,7 +52,8 @@ def main():
     w = torch.full((K, B), 1.0 / B, device=dev)
     params = torch.stack([spec.init_params(k) for k in range(K)]).to(dev)
     prog = HeaMfmaProgram(spec, dev, use_spec=None if args.spec is None else bool(args.spec))
-    print(json.dumps({"spec": prog.spec_active, "spec_passes": prog.spec_passes()}), flush=True)
+    print(json.dumps({"spec": prog.spec_active, "spec_passes": prog.spec_passes(samples=K * B),
+                      "readout_mode": prog.readout_mode(K * B)}), flush=True)
     for _ in range(3):                                  # warm caches / clocks
         prog.loss_and_grads(x, y, w, params, spec)
     dbg = prog.stamp_buffers()
