@@ -41,6 +41,12 @@ namespace HEA_NS {
 #ifdef QFX_HEA_SPEC
 constexpr bool SPEC = true;
 #define HEA_OP_LOOP _Pragma("unroll")
+// QFX_HEA_OBS_LOAD (prelude; only the last adjoint pass, whose first op is OP_OBS and which loads no lambda): the tile
+// load writes the seeded lambda words itself (seed_tile_il) and the op loop starts behind the OBS record.
+#ifndef QFX_HEA_OBS_LOAD
+#define QFX_HEA_OBS_LOAD 0
+#endif
+constexpr bool OBS_LOAD = QFX_HEA_OBS_LOAD != 0;
 struct PA : PassArgs {
   static constexpr int n = hea_spec::N, t = hea_spec::T, c = hea_spec::CB, lo = hea_spec::LO, hi = hea_spec::HI;
   static constexpr int n_tiles = hea_spec::NTILES, nops = hea_spec::NOPS, C = hea_spec::NCLS;
@@ -78,6 +84,7 @@ struct OpRec {
 };
 #else
 constexpr bool SPEC = false;
+constexpr bool OBS_LOAD = false;
 #define HEA_OP_LOOP
 using PA = PassArgs;
 struct OpRec {
@@ -203,6 +210,67 @@ __device__ __forceinline__ void load_tile_il(const PA& a, const uint32_t* psrc, 
     }
   }
 }
+
+#ifdef QFX_HEA_SPEC
+// Seeding tile load of the pass whose first op is the observable (OBS_LOAD), in two halves.  load_tile_issue requests
+// the thread's psi quads; seed_tile_il writes them to LDS with the lambda word of every LDS word w beside its psi
+// word, lambda = (sum_c +-r_c) psi exactly as obs_op forms it (the sum starts from 0.f, classes ascending, the
+// products by +-1 exact), so the OBS sweep over the tile, its LDS round trip and its barrier go away.  After
+// quad_perm a thread holds LDS words w0 .. w0 + 3, w0 = wt ^ wi with
+//   wt = (4 tid ^ h_q) & ~3                per thread: one parity per class, folded into the weight's sign once
+//   wi = (4 NT i ^ h(4 NT i / 32)) & ~3    per quad index i: a constant, as is the word index j < 4
+// and class c's sign parity(w & om_c) ^ parity(fixed & of_c) is GF(2)-linear in w.  Between the halves the caller
+// forms the weights r[c] in registers, while the tile is in flight.
+template <int NT, int TB>
+__device__ __forceinline__ void load_tile_issue(const PA& a, const uint32_t* psrc, uint4* v, int tid, int T,
+                                                uint32_t fixed) {
+  constexpr int MQ = (1 << TB) / (4 * NT);
+#pragma unroll
+  for (int i = 0; i < MQ; ++i) {
+    const uint32_t q = 4u * (tid + NT * i);
+    v[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (q < (uint32_t)T) v[i] = *(const uint4*)&psrc[mem_of(q, a, fixed)];
+  }
+}
+
+template <int NC, int NT, int TB>
+__device__ __forceinline__ void seed_tile_il(const PA& a, const uint4* v, uint32_t* tile, int tid, int T, uint32_t h_q,
+                                             uint32_t fixed, const float* r) {
+  constexpr int MQ = (1 << TB) / (4 * NT);
+  const OpRec obs{0};
+  const uint32_t wt = ((4u * (uint32_t)tid) ^ h_q) & ~3u;
+  float rt[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) rt[c] = (par(wt & obs.cls_om(c)) ^ par(fixed & obs.cls_of(c))) ? -r[c] : r[c];
+#pragma unroll
+  for (int i = 0; i < MQ; ++i) {
+    const uint32_t q = 4u * (tid + NT * i);
+    if (q < (uint32_t)T) {
+      const uint32_t hi = swz(a, (uint32_t)(4 * NT / 32) * i), h = h_q ^ hi;
+      const uint32_t wi = ((uint32_t)(4 * NT * i) ^ hi) & ~3u;
+      const uint32_t w0 = (q ^ h) & ~3u;           // = wt ^ wi (masked last: the b128 stores need the alignment)
+      const uint4 pv = quad_perm(v[i], h & 3u);
+      const uint32_t pw[4] = {pv.x, pv.y, pv.z, pv.w};
+      uint32_t lw[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float fsum = 0.f;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) fsum += par((wi | (uint32_t)j) & obs.cls_om(c)) ? -rt[c] : rt[c];
+        const float2 f = unpack_h2(pw[j]);
+        lw[j] = pack_h2(fsum * f.x, fsum * f.y);
+      }
+      // Two 16-byte stores per quad, as load_tile_il's.  Issued as asm: left to itself the compiler keeps the psi and
+      // lambda words where they were computed and emits four ds_write2_b32 per quad instead - twice the LDS
+      // instructions, each on a quarter of the banks.  (LDS operations complete in order and op_barrier waits for
+      // lgkmcnt(0) itself, so the wait-count pass need not know these stores.)
+      const uint32_t la = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)&tile[2 * w0];
+      const u4v o0 = {pw[0], lw[0], pw[1], lw[1]}, o1 = {pw[2], lw[2], pw[3], lw[3]};
+      __asm__ volatile("ds_write_b128 %0, %1\n\tds_write_b128 %0, %2 offset:16" ::"v"(la), "v"(o0), "v"(o1) : "memory");
+    }
+  }
+}
+#endif
 
 template <int NT, int TB>
 __device__ __forceinline__ void store_lam_il(const PA& a, uint32_t* dst, const uint32_t* tile, int tid, int T,
@@ -1163,10 +1231,18 @@ __device__ __forceinline__ void adj_pass(const PA& a, int bid) {
     fo_s[tid] = a.fo_tab[(size_t)tile_id * a.nops + tid];
     QFX_DCHECK(fo_s[tid] == op_fo_global(a.ops + (size_t)tid * OPW, fixed));
   }
+  // the first op the loop runs: 1 when the tile load seeds lambda in place of the OBS record (OBS_LOAD).  Records,
+  // fo_tab rows, fragment and gradient indices keep their positions, and so does the fragment slot parity (o & 1).
+  constexpr int O0 = OBS_LOAD ? 1 : 0;
 #ifdef QFX_HEA_SPEC
-  if (a.nops > 0) {
-    const int fi0[2] = {OpRec{0}.fidx(0), OpRec{0}.fidx(1)};
-    dma_frags(a, k, fi0, lane, wave, frag_s[0]);
+#if QFX_HEA_OBS_LOAD
+  static_assert(hea_spec::ADJ && hea_spec::CODE[0] == OP_OBS && hea_spec::LOAD_LAM == 0,
+                "OBS_LOAD: the last adjoint pass, whose first op is the observable");
+#endif
+  if (a.nops > O0) {
+    constexpr int OF = O0 < PA::nops ? O0 : 0;
+    const int fi0[2] = {OpRec{OF}.fidx(0), OpRec{OF}.fidx(1)};
+    dma_frags(a, k, fi0, lane, wave, frag_s[OF & 1]);
   }
 #else
   if (tid < OPW && a.nops > 0) opw2[0][tid] = a.ops[tid];
@@ -1189,10 +1265,40 @@ __device__ __forceinline__ void adj_pass(const PA& a, int bid) {
     }
   }
   st.mark(PH_PRO);
+#ifdef QFX_HEA_SPEC
+  // OBS_LOAD: every thread requests the sample's readout weights (one address per workgroup) ahead of its psi quads,
+  // forms r_c = w_c / rho in registers while the tile is in flight - the division is the correctly rounded one, so
+  // every thread holds bitwise the values thread 0 puts into rsc - and writes the seeded image as its quads arrive:
+  // no LDS round trip for the weights and no barrier before the one that opens the op loop.  (The fused readout,
+  // whose weights come from the partials, is not compiled into this variant: hea_spec_launch refuses it.)
+  if constexpr (OBS_LOAD) {
+    float wv[CMAX], r[NCK];
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) wv[c] = c < a.C ? a.wread[(size_t)s * a.C + c] : 0.f;
+    uint4 pq[(1 << TB) / (4 * NT)];
+    load_tile_issue<NT, TB>(a, a.psi_in + (size_t)s * N, pq, tid, T, fixed);
+    float rho = 0.f;
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) {
+      if (c >= a.C) break;
+      rho = fmaxf(rho, fabsf(wv[c]));
+    }
+    if (rho == 0.f) rho = 1.f;
+#pragma unroll
+    for (int c = 0; c < NCK; ++c) r[c] = c < a.C ? wv[c] / rho : 0.f;
+    if (tid == 0) {
+#pragma unroll
+      for (int c = 0; c < NCK; ++c) rsc[c] = r[c];
+      rsc[CMAX] = rho;
+      rsc[CMAX + 1] = PK_SCALE / (a.scale * a.scale);
+    }
+    seed_tile_il<NCK, NT, TB>(a, pq, tile, tid, T, h_q, fixed, r);
+  } else
+#endif
   load_tile_il<NT, TB>(a, a.psi_in + (size_t)s * N, a.load_lam ? a.lam_in + (size_t)s * N : nullptr, tile, tid, T, h_q,
                        fixed);
 
-  if (a.ro_fuse ? tid == NT - 64 : tid == 0) {
+  if (!OBS_LOAD && (a.ro_fuse ? tid == NT - 64 : tid == 0)) {   // (OBS_LOAD: rsc is filled above)
     float wv[CMAX];
     if (a.ro_fuse) {
       // lane 0 of the last wave: partials and parameters gathered from its wave's lanes (one load round trip); every
@@ -1298,10 +1404,10 @@ __device__ __forceinline__ void adj_pass(const PA& a, int bid) {
     epi |= sl << (8 * i);
   }
   HEA_OP_LOOP
-  for (int o = 0; o < a.nops; ++o) {
+  for (int o = O0; o < a.nops; ++o) {
     // op o's record and fragments were written during op o - 1; the other buffers were last read at the
     // start of op o - 1, which every wave has finished at this barrier, so op o + 1's go there right away
-    if (o > 0) {
+    if (o > O0) {
       op_barrier(wave);
       st.mark(PH_BAR);
     }

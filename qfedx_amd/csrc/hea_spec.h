@@ -17,10 +17,13 @@ struct HeaSpecDesc {
   int n = 0, t = 0, c = 0, lo = 0, hi = 0, ncls = 0;
   int gen = 0, load_lam = 0, store_lam = 0, n_regions = 0;
   int hrow[5] = {0, 0, 0, 0, 0};
+  bool obs_load = false;            // requested: the tile load seeds lambda in place of a leading OP_OBS record
   std::vector<int> ops;             // [nops][128] op records
   std::vector<int> fidx;            // [nops][2] fragment indices
 };
 
+// obs_load as compiled: only an adjoint pass that loads no lambda and whose first op is OP_OBS has a seeding load
+bool hea_spec_obs_load(const HeaSpecDesc& d);
 std::string hea_spec_prelude(const HeaSpecDesc& d);
 std::string hea_spec_source(const HeaSpecDesc& d);
 std::string hea_spec_key(const HeaSpecDesc& d, const std::string& include_dir, const std::string& arch);

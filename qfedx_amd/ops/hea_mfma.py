@@ -77,6 +77,13 @@ def split_readout_default():
     return None if env == "" else env != "0"
 
 
+def obs_load_default() -> bool:
+    """``QFEDX_HEA_OBS_LOAD`` = 1 / 0: the per-plan kernel of the last adjoint pass seeds lambda while it loads its
+    tile and runs no observable op (csrc/hea_mfma.hip seed_tile_il) / keeps the op, i.e. compiles exactly the text it
+    compiled before the seeding load existed.  Read when a program is built (``HeaMfmaProgram.obs_at_load``)."""
+    return os.environ.get("QFEDX_HEA_OBS_LOAD", "1" if OBS_LOAD_DEFAULT else "0") != "0"
+
+
 _SPEC_WARNED = False
 _NO_KEYS = torch.zeros(0, dtype=torch.int64)
 _NODBG = torch.zeros(0, dtype=torch.int64)     # no stall-attribution buffer (stamps build only)
@@ -90,6 +97,12 @@ FUSED_ADAM_MAX_BLOCKS = 256   # hea_grad_reduce blocks (clients x gradient ops) 
 # 0.166 -> 0.159, 256 0.270 -> 0.253, 512 0.480 -> 0.444, 2048 1.659 -> 1.509 (profiles/split_readout_ab.txt).  Never
 # below 64: steps of a few samples stay fused whatever a box measures.
 SPLIT_READOUT_MIN_SAMPLES = 128
+# The per-plan last adjoint pass seeds lambda during its tile load (obs_load_default): bitwise the same results.
+# Measured, 16q x 3L, clients x 32 samples, ms per round parent -> knob 1, two boxes (profiles/obs_at_load_ab.txt):
+# 64 clients 1.589 -> 1.555 (3 x the parent's spread: 0.036, missed by 0.001) and 1.684 -> 1.663 (0.012, met), every
+# knob-1 run below every parent run; 8 clients 0.255 -> 0.250, inside three spreads (0.016): a tie.  Compiled into the
+# one kernel a pass has, so not gated by sample count.
+OBS_LOAD_DEFAULT = True
 
 
 class HeaMfmaProgram:
@@ -208,6 +221,8 @@ class HeaMfmaProgram:
         self.spec_requested = spec_default() if use_spec is None else bool(use_spec)
         # split-readout steps (readout_mode): None = by sample count, True / False = wherever possible / never
         self.split_readout = split_readout_default()
+        # the per-plan kernel of a pass that starts with the observable op seeds lambda in its tile load (spec_cfg)
+        self.obs_at_load = obs_load_default()
         if self.spec_requested:
             self.prepare_spec()
 
@@ -270,7 +285,7 @@ class HeaMfmaProgram:
         from .. import _build
         return [self.n, p.t, p.c, p.lo, p.hi, self.C, gen, load_lam, store_lam,
                 self.n_regions[j] if adjoint else 0] + [int(h) for h in p.H] + \
-               [int(self.bf16), int(_build.variant() == "stamps"), gate_lo]
+               [int(self.bf16), int(_build.variant() == "stamps"), gate_lo, int(self.obs_at_load)]
 
     def prepare_spec(self) -> bool:
         """Compile (or load from ``QFEDX_JIT_CACHE``) the forward and adjoint kernel of every pass; on a failure warn

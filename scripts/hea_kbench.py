@@ -69,7 +69,9 @@ def main():
            "spec_passes": (prog.spec_passes(samples=S) if hasattr(prog, "readout_mode") else
                            prog.spec_passes() if hasattr(prog, "spec_passes") else None),
            # (fused: the last adjoint pass computes the readout, on the interpreter; split: hea_readout_rec + per plan)
-           "readout_mode": prog.readout_mode(S) if hasattr(prog, "readout_mode") else None}
+           "readout_mode": prog.readout_mode(S) if hasattr(prog, "readout_mode") else None,
+           # (QFEDX_HEA_OBS_LOAD: the per-plan last adjoint pass seeds lambda in its tile load)
+           "obs_at_load": getattr(prog, "obs_at_load", None)}
 
     def timeit(fn, name, nbytes):
         fn()

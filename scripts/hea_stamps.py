@@ -53,7 +53,10 @@ def main():
     params = torch.stack([spec.init_params(k) for k in range(K)]).to(dev)
     prog = HeaMfmaProgram(spec, dev, use_spec=None if args.spec is None else bool(args.spec))
     print(json.dumps({"spec": prog.spec_active, "spec_passes": prog.spec_passes(samples=K * B),
-                      "readout_mode": prog.readout_mode(K * B)}), flush=True)
+                      "readout_mode": prog.readout_mode(K * B),
+                      # QFEDX_HEA_OBS_LOAD: the per-plan last adjoint pass seeds lambda in its tile load (phase LOAD,
+                      # no OTHER) instead of running the observable op
+                      "obs_at_load": prog.obs_at_load}), flush=True)
     for _ in range(3):                                  # warm caches / clocks
         prog.loss_and_grads(x, y, w, params, spec)
     dbg = prog.stamp_buffers()
