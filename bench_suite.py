@@ -73,9 +73,40 @@ SUITE = {
                           "fp16 MFMA engine)", None),
     "vqc48q_mps64": ("configs/mps_48q_64clients.yaml", [],
                      "client local-steps/sec (48-qubit VQC x 64 clients, MPS tensor-network backend)", None),
+    # amplitude-encoded 28 x 28 digits in 10 qubits: the MFMA engine (staged fp16 input states) against the fp32 VALU
+    # engine, which auto routing keeps for amplitude inputs
+    "vqc10q_amp64_mfma": ("configs/digits_amplitude_10q.yaml", [],
+                          "client local-steps/sec (10-qubit amplitude-encoded VQC x 64 clients, fp16 MFMA engine)", None),
+    "vqc10q_amp64": ("configs/digits_amplitude_10q.yaml", ["model.state_dtype=fp32"],
+                     "client local-steps/sec (10-qubit amplitude-encoded VQC x 64 clients)", None),
     "vqc4q_2_cpu": ("configs/baseline1_4q_2clients_cpu.yaml", ["train.local_steps=1"],
                     "client local-steps/sec (4-qubit VQC x 2 clients, CPU gloo)", None),
 }
+
+
+def amp_precision_check(runner, batch: int) -> dict:
+    """``bench.precision_check`` for an amplitude-encoded VQC: one untimed adjoint VJP of this rank's clients on the
+    MFMA engine and on the fp32 VALU engine from the same raw feature rows (each engine encodes them on the device)."""
+    import torch
+    from qfedx_amd.ops.statevec_hip import HipProgram
+    eng = runner.adapter.engine
+    spec = runner.adapter.spec
+    if getattr(eng, "hip", None) is None or isinstance(eng.hip, HipProgram):
+        return {}
+    init = runner.store.X[:, :batch].float()
+    xang = spec.encode_features(init)
+    K, B = init.shape[:2]
+    th = runner.params[: spec.n_theta].float()[None].expand(K, -1).contiguous()
+    g = torch.Generator(device="cpu").manual_seed(1234)
+    w = (torch.randn(K * B, spec.n_classes, generator=g) / B).to(init.device)
+    z_m, g_m = eng.hip.vjp(xang, th, w, init=init)
+    ref = HipProgram(eng.ops, eng.coef, spec.n_qubits, spec.readout, init.device, n_theta=spec.n_theta,
+                     state_dtype="fp32", jit=False, x_width=spec.x_width)
+    z_r, g_r = ref.vjp(xang, th, w, init=init.reshape(K * B, -1))     # (HipProgram.vjp takes its rows flat)
+    torch.cuda.synchronize()
+    return {"max_abs_err_expz": float((z_m - z_r).abs().max()), "max_abs_err_grad": float((g_m - g_r).abs().max()),
+            "max_abs_grad": float(g_r.abs().max()), "precision_ref": "fp32 VALU engine (interpreter kernels)",
+            "precision_samples": int(K * B)}
 
 
 def main():
@@ -148,7 +179,9 @@ def main():
                          "epsilon": round(float(runner.accountant.get_epsilon(cfg.privacy.delta)), 4),
                          "deterministic_noise": cfg.privacy.deterministic_noise}
         eng = getattr(runner.adapter, "engine", None)
-        if kind == "vqc" and backend == "hip":
+        if kind == "vqc" and backend == "hip" and runner.adapter.spec.amplitude:
+            rec.update(amp_precision_check(runner, t.batch_size))   # untimed: MFMA vs fp32 VALU engine, same raw rows
+        elif kind == "vqc" and backend == "hip":
             from bench import precision_check
             rec.update(precision_check(runner, t.batch_size))     # untimed: MFMA vs fp32 VALU engine
             if cfg.model.state_dtype == "mfma" and "bf16" in path:

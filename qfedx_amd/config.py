@@ -48,7 +48,9 @@ class ModelConfig:
     init_std: float = 0.1
     state_dtype: str = "auto"           # auto (mfma when eligible on HIP, else fp32) | fp32 | mfma (fp16 MFMA engine,
                                         # hardware-efficient ansatz) | bf16 (bf16 MFMA engine when eligible, else
-                                        # bf16 storage on the VALU pass engine) | bf16_valu
+                                        # bf16 storage on the VALU pass engine) | bf16_valu.  feature_map: amplitude
+                                        # stays on the VALU engine under auto / bf16; mfma | fp16 | mfma_bf16 run it
+                                        # on the MFMA engine (staged input states, >= 8 qubits)
     simulator: str = "statevector"      # statevector | mps (tensor network past statevector memory) | density
                                         # (exact Kraus channels, <= 10 qubits; auto for noise.kind=amplitude)
     mps_chi: int = 64                   # MPS bond-dimension cap (exact while the circuit's bound fits)

@@ -19,7 +19,11 @@ def resolve_state_dtype(state_dtype: str, spec, backend: str, noise) -> str:
     """``auto``: the fp16 MFMA engine (ops/hea_mfma.py) on the HIP backend for the specs it covers (CNOT-chain
     or no entangler, angle features, >= 8 qubits, no gate noise; readout confusion and shots are applied by its
     readout kernels), the fp32 VALU pass engine otherwise.  ``bf16``: the bf16 MFMA engine (``mfma_bf16``) where the
-    MFMA engine applies, else bf16 storage on the VALU pass engine; ``bf16_valu`` forces the latter."""
+    MFMA engine applies, else bf16 storage on the VALU pass engine; ``bf16_valu`` forces the latter.
+    Amplitude-encoded specs stay on the VALU engine under ``auto`` and ``bf16`` (``auto`` would otherwise trade fp32
+    states for fp16 ones silently, and which engine is faster at 8-12 qubits depends on the shape); the explicit
+    values ``mfma`` / ``fp16`` / ``mfma_bf16`` are passed through and run them on the MFMA engine when
+    ``hea_plan.eligible_amplitude`` holds (chain or no entangler, no gate noise, 8..30 qubits, <= 8 classes)."""
     if state_dtype == "bf16_valu":
         return "bf16"
     if state_dtype == "bf16":

@@ -117,6 +117,8 @@ class VQCEngine:
         self._tiles_fitted = True
         if hip.tile_bits < 14 or samples <= 0:
             return False
+        if hip.n <= 13:          # the tile already is the whole state (e.g. 8-12 qubit amplitude programs): same plan
+            return False
         cus = torch.cuda.get_device_properties(self.device).multi_processor_count
         if samples * hip.tiles_last >= 2 * cus:
             return False

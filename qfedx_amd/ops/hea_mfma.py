@@ -12,7 +12,10 @@
 
 It exposes the subset of ``HipProgram``'s interface the engine / trainer use (``expz``, ``vjp``,
 ``loss_and_grads``, ``private_workspace``), so ``VQCEngine(..., backend="hip", state_dtype="mfma")``
-swaps it in for circuits ``hea_plan.eligible`` accepts.  Amplitudes are stored as fp16 scaled by
+swaps it in for circuits ``hea_plan.eligible`` accepts.  Amplitude-encoded circuits (``hea_plan.eligible_amplitude``)
+run too: real ``init`` rows are normalised and written in the storage format by ``hea_amp_stage`` (csrc/hea_amp.hip),
+forward pass 0 loads that buffer instead of generating a product state, and layer 1 is an ordinary rotation layer of
+the plan.  Amplitudes are stored as fp16 scaled by
 2^(n/2) (unit-magnitude typical values); MFMAs accumulate in fp32 and the unitaries carry a hi/lo fp16
 split, so the only rounding is the fp16 state between ops (~2^-12 relative per op).
 """
@@ -25,8 +28,8 @@ import numpy as np
 import torch
 
 from ._ext import ext
-from .hea_plan import (OP_APPLY, OP_APPLY2, OP_BACK, OP_BACK2, OP_GRAD2, OP_GRAD_L1, OP_READOUT, TILE_BITS, W_CODE, build_plan, eligible, fo_table, obs_table,
-                       pass_programs)
+from .hea_plan import (OP_APPLY, OP_APPLY2, OP_BACK, OP_BACK2, OP_GRAD2, OP_GRAD_L1, OP_READOUT, TILE_BITS, W_CODE, build_plan, eligible,
+                       eligible_amplitude, fo_table, obs_table, pass_programs)
 
 ADJ_TILE_BITS = 13   # adjoint tiles: 2^13 amplitudes x (psi, lambda) = 64 KB of LDS -> two workgroups per CU
 
@@ -39,7 +42,7 @@ def _same_passes(a, b) -> bool:
         return [sorted((g.slot, g.layer, tuple(g.qubits), g.frame) for g in p.groups) for p in plan.passes]
     return a.n_slots == b.n_slots and sig(a) == sig(b)
 
-_FEATURE = {"ry": 0, "rx": 1, "rz": 2}
+_FEATURE = {"ry": 0, "rx": 1, "rz": 2, "amplitude": 0}      # (an amplitude program never generates: unused)
 
 
 def _frag_index(ops: np.ndarray) -> torch.Tensor:
@@ -114,10 +117,14 @@ class HeaMfmaProgram:
             raise ValueError(f"MFMA engine storage must be fp16 | bf16, got {storage!r}")
         self.storage = storage
         self.bf16 = storage == "bf16"
-        if not eligible(spec):
-            raise ValueError("the MFMA engine covers angle-encoded RX/RZ + CNOT-chain VQCs with 8..30 qubits, "
-                             "no gate noise and <= 8 classes")
+        if not (eligible(spec) or eligible_amplitude(spec)):
+            raise ValueError("the MFMA engine covers angle-encoded (hea_plan.eligible) and amplitude-encoded "
+                             "(hea_plan.eligible_amplitude) RX/RZ + CNOT-chain VQCs with 8..30 qubits, no gate noise "
+                             "and <= 8 classes")
         self.spec = spec
+        # amplitude program: forward pass 0 loads the staged input states (``_stage``) instead of generating the
+        # layer-1 product state, and every layer's rotations are group ops
+        self.amplitude = bool(spec.amplitude)
         self.n = spec.n_qubits
         self.C = spec.n_classes
         self.n_theta = spec.n_theta
@@ -279,7 +286,7 @@ class HeaMfmaProgram:
         """Constants pass j's per-plan kernel is compiled with (hea_bindings.cpp spec_desc)."""
         p = self.passes[j][3] if adjoint else self.passes[j][0]
         J = self.n_passes
-        gen, load_lam, store_lam = (0, int(j < J - 1), int(j > 0)) if adjoint else (int(j == 0), 0, 0)
+        gen, load_lam, store_lam = (0, int(j < J - 1), int(j > 0)) if adjoint else (int(self._gen(j)), 0, 0)
         glo = os.environ.get("QFEDX_EXTRA_HIPFLAGS", "")
         gate_lo = 0 if "-DQFX_HEA_GATE_LO=0" in glo else (1 if "-DQFX_HEA_GATE_LO=1" in glo else -1)
         from .. import _build
@@ -299,8 +306,9 @@ class HeaMfmaProgram:
             for j, ((f, ff), (a, fa)) in enumerate(self._host_progs):
                 # The forward pass that generates the layer-1 product state stays on the interpreter: compiled per
                 # plan, its fp32 complex products came out different in the last bit on a share of the amplitudes (FMA
-                # contraction follows the surrounding code), and the two paths must agree bitwise.
-                if 0 < j <= self.fwd_last and len(f):
+                # contraction follows the surrounding code), and the two paths must agree bitwise.  An amplitude
+                # program has no such pass: its pass 0 loads staged states like every later pass.
+                if not self._gen(j) and j <= self.fwd_last and len(f):
                     fwd[j], k = C.hea_spec_prepare(False, f, ff, self.spec_cfg(j, False), JIT_CACHE, CSRC, ARCH)
                     keys.append(k)
                 if len(a):
@@ -357,8 +365,14 @@ class HeaMfmaProgram:
         """Tiles per sample of the pass that reads out <Z> (the last forward pass that runs)."""
         return 1 << (self.n - self.passes[self.fwd_last][0].t)
 
+    def _gen(self, j: int) -> bool:
+        """Forward pass j generates the layer-1 product state in its tile (pass 0 of an angle program)."""
+        return j == 0 and not self.amplitude
+
     def _geom(self, p, gen, load_lam, store_psi, store_lam, B, p_stride, S, x_stride, K, in_rep: int = 1,
               n_regions: int = 0, shared: bool = False):
+        if self.amplitude:       # no pass reads feature angles (gen = 0 everywhere): the dummy column's stride is moot
+            x_stride = max(int(x_stride), self.n)
         return [self.n, p.t, p.c, p.lo, p.hi, 1 << (self.n - p.t), int(gen), int(load_lam), int(store_psi),
                 int(store_lam), B, self.C, self.n_theta, p_stride, self.feature, S, x_stride, self.n_slots,
                 self.slab_tiles, K] + [int(h) for h in p.H] + [self.n_gradops, int(in_rep), int(self.bf16),
@@ -379,8 +393,40 @@ class HeaMfmaProgram:
             ext().hea_frags(params, params.shape[1], self.slot_tab, self.n_slots, K, fr, self.bf16)
         return fr
 
+    def _stage(self, init: torch.Tensor, K: int, B: int, tag: str = "") -> torch.Tensor:
+        """Real ``init`` [K, B, F <= 2^n] raw amplitudes -> psi_in of forward pass 0 in a workspace buffer (owned by a
+        captured round like every other): zero padded, normalised with a float64 norm (a zero row -> the uniform
+        state), scaled and rounded once to the storage format on the device (csrc/hea_amp.hip)."""
+        if init.dim() != 3 or init.shape[0] != K or init.shape[1] != B:
+            raise ValueError(f"init must be [K, B, F] = [{K}, {B}, <= 2^{self.n}], got {tuple(init.shape)}")
+        if init.shape[2] < 1 or init.shape[2] > (1 << self.n):
+            raise ValueError(f"init has {init.shape[2]} amplitudes per sample, the state 2^{self.n}")
+        x = init.reshape(K * B, init.shape[2])
+        if x.dtype != torch.float32 or x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+            x = x.float().contiguous()
+        psi = self._buf(f"{tag}amp", (K * B) << self.n, torch.int32)
+        ext().hea_amp_stage(x, self.n, psi, self.scale, self.bf16)
+        return psi
+
+    def _check_init(self, init) -> None:
+        """Refuse an ``init`` this program cannot start from, saying why."""
+        if not self.amplitude:
+            if init is not None:
+                raise ValueError("this MFMA program starts from the angle feature map: it takes no initial states "
+                                 "(init is for feature_map='amplitude' specs)")
+        elif init is None:
+            raise ValueError("an amplitude-encoded MFMA program needs init [K, B, F <= 2^n] raw amplitudes")
+        elif init.is_complex():
+            raise ValueError("the MFMA engine encodes real amplitudes itself (normalised, real states); explicit "
+                             "complex initial states run on the fp32 VALU engine (state_dtype=fp32)")
+
+    def _start(self, init, K: int, B: int, tag: str = ""):
+        """Staged input states of an amplitude program, None for an angle program."""
+        self._check_init(init)
+        return self._stage(init, K, B, tag) if self.amplitude else None
+
     def _forward(self, x, params, fr, K, B, part, store_last: bool = False, tag: str = "", dbg=None,
-                 shared: bool = False):
+                 shared: bool = False, psi0=None):
         """Forward passes up to the readout pass ``fwd_last``; returns the stored pass outputs (all of them with
         ``store_last``: the adjoint starts each pass from its output; identity passes after ``fwd_last`` alias
         its output).  ``tag`` names the workspaces; ``dbg`` (stamps build): per-pass stall-attribution buffers."""
@@ -397,8 +443,10 @@ class HeaMfmaProgram:
             # evaluation only needs the previous pass output: two ping-pong buffers instead of one per pass
             name = f"{tag}psi{j}" if store_last else f"{tag}pe{j % 2}"
             out = self._buf(name, N, torch.int32) if keep else empty
-            psi_in = stored[-1] if j > 0 else empty
-            geom = self._geom(p, j == 0, False, keep, False, B, params.shape[1], S, x.shape[1], K, shared=shared)
+            psi_in = stored[-1] if j > 0 else (psi0 if psi0 is not None else empty)
+            if self._gen(j) != (psi_in.numel() == 0):
+                raise RuntimeError("forward pass without a start: amplitude programs need staged states")
+            geom = self._geom(p, self._gen(j), False, keep, False, B, params.shape[1], S, x.shape[1], K, shared=shared)
             C.hea_pass(False, fwd[0], fwd[1], fwd[2], geom, self.scale, psi_in, out, empty, empty, x, params, fr, fempty,
                        part if j == R else fempty, fempty, dbg[f"fwd{j}"] if dbg else _NODBG,
                        spec=self._count(self.spec_fwd[j]))
@@ -439,7 +487,7 @@ class HeaMfmaProgram:
 
     def _prep(self, xang, params):
         K, B, F = xang.shape
-        if F < self.n:
+        if F < self.n and not self.amplitude:     # (an amplitude program reads no feature angles)
             raise ValueError(f"expected >= {self.n} feature angles per sample, got {F}")
         x = xang.reshape(K * B, F).float().contiguous()
         p = params.float().contiguous()
@@ -451,9 +499,8 @@ class HeaMfmaProgram:
     @torch.no_grad()
     def expz(self, xang: torch.Tensor, theta: torch.Tensor, noise=None, keys=None, step: int = 0,
              init: torch.Tensor | None = None) -> torch.Tensor:
-        if init is not None:
-            raise ValueError("the MFMA engine starts from the angle feature map (no initial states)")
         x, th, K, B = self._prep(xang, theta)
+        self._check_init(init)
         if th.shape[1] < self.n_theta + 2 * self.C:    # pad theta-only rows to the kernel's param stride
             th = torch.cat([th, th.new_zeros(K, self.n_theta + 2 * self.C - th.shape[1])], 1)
         S = K * B
@@ -466,7 +513,8 @@ class HeaMfmaProgram:
             thc = th[k0:k1] if Kc < K else th
             fr = self._frags(thc, k1 - k0)
             part = self._buf("part", Sc * self.tiles_last * self.C, torch.float32)
-            self._forward(x[k0 * B:k1 * B], thc, fr, k1 - k0, B, part)
+            psi0 = self._stage(init[k0:k1], k1 - k0, B) if self.amplitude else None     # staged per client chunk
+            self._forward(x[k0 * B:k1 * B], thc, fr, k1 - k0, B, part, psi0=psi0)
             ext().readout_sum(part, self.tiles_last, self.C, Sc, out[k0 * B * self.C:k1 * B * self.C])
         if noise is not None:
             from .statevec_hip import _keys
@@ -476,15 +524,14 @@ class HeaMfmaProgram:
     @torch.no_grad()
     def vjp(self, xang: torch.Tensor, theta: torch.Tensor, w: torch.Tensor, init: torch.Tensor | None = None):
         """Adjoint VJP of sum_c w[s, c] <Z_c>_s -> (<Z> [S, C], d/dtheta [K, n_theta])."""
-        if init is not None:
-            raise ValueError("the MFMA engine starts from the angle feature map (no initial states)")
         x, th, K, B = self._prep(xang, theta)
+        psi0 = self._start(init, K, B)
         if th.shape[1] < self.n_theta + 2 * self.C:
             th = torch.cat([th, th.new_zeros(K, self.n_theta + 2 * self.C - th.shape[1])], 1)
         S = K * B
         fr = self._frags(th, K)
         part = self._buf("part", S * self.tiles_last * self.C, torch.float32)
-        stored = self._forward(x, th, fr, K, B, part, store_last=True)
+        stored = self._forward(x, th, fr, K, B, part, store_last=True, psi0=psi0)
         z = self._buf("expz", S * self.C, torch.float32)
         ext().readout_sum(part, self.tiles_last, self.C, S, z)
         wr = w.reshape(S, self.C).float().contiguous()
@@ -498,6 +545,9 @@ class HeaMfmaProgram:
     def shift_owners(self) -> list:
         """Per forward pass j <= fwd_last: the theta indices whose rotation it applies (layer 1 is generated in
         pass 0; rotation group g of pass j carries theta_slot(layer, q) and its phase partner)."""
+        if self.amplitude:
+            raise ValueError("prefix-reuse parameter shift is angle-only: an amplitude program's shifted circuits run "
+                             "as parameter rows of expz(init=...) (VQCEngine.param_shift_batched)")
         own = [[] for _ in range(self.fwd_last + 1)]
         for q in range(self.n):
             own[0] += [self.plan.theta_slot(1, q), self.plan.theta_slot(1, q) + 1]
@@ -623,6 +673,9 @@ class HeaMfmaProgram:
         f', so m is not needed (no +pi branches).  Work is chunked over clients and over shifted rows to fit
         ``_shift_budget`` (0.4 of free HBM).  ``exact_only``: skip the readout model (tests).
         w = dL/d<Z>_noisy [K, B, C] -> [K, n_theta]."""
+        if self.amplitude:
+            raise ValueError("prefix-reuse parameter shift is angle-only: an amplitude program's shifted circuits run "
+                             "as parameter rows of expz(init=...) (VQCEngine.param_shift_batched)")
         K, B, C = w.shape
         P = self.n_theta
         noisy = noise is not None and not exact_only
@@ -687,7 +740,7 @@ class HeaMfmaProgram:
         return [self.slot_tab, self._buf("pfrags", self.n_slots * 4 * 128 * 4, torch.int32)]
 
     def _step(self, x, p, yy, ww, K, B, loss, correct, grad, expz, noise, keys, step, adam=None, dbg=None,
-              shared_frags=None, fed=None):
+              shared_frags=None, fed=None, psi0=None):
         """Forward, readout + CE, adjoint and gradient reduction of clients [0, K).
         ``adam`` = (tensors, hyper) from ``BatchedOptimizer.fused_adam``: the clients' Adam step runs in the
         gradient reduction's epilogue (one launch fewer per local step).  ``dbg``: stall-attribution buffers per
@@ -699,7 +752,7 @@ class HeaMfmaProgram:
         part = self._buf("part", S * self.tiles_last * self.C, torch.float32)
         wread = self._buf("wread", S * self.C, torch.float32)
         gslab = self._buf("gslab", S * self.slab_tiles * self.n_gradops * 32, torch.int64)
-        stored = self._forward(x, p, fr, K, B, part, store_last=True, dbg=dbg, shared=shared)
+        stored = self._forward(x, p, fr, K, B, part, store_last=True, dbg=dbg, shared=shared, psi0=psi0)
         # Fused readout: the first adjoint pass computes each sample's <Z>, cross entropy and dL/d<Z> from the readout
         # partials, and the gradient reduction sums the clients' loss, hits and readout gradients - one launch fewer
         # per local step.
@@ -750,9 +803,8 @@ class HeaMfmaProgram:
         ``fused_opt`` = (BatchedOptimizer, active): with params updated in place (a contiguous fp32 tensor) and HIP
         Adam, the optimizer step runs in the gradient reduction's epilogue and the result says ``opt_done``;
         otherwise the caller steps the optimizer itself."""
-        if init is not None:
-            raise ValueError("the MFMA engine starts from the angle feature map (no initial states)")
         x, p, K, B = self._prep(xang, params)
+        psi0 = self._start(init, K, B)
         S = K * B
         yy = y.reshape(S).long().contiguous()
         ww = wmask.reshape(S).float().contiguous()
@@ -773,7 +825,7 @@ class HeaMfmaProgram:
             adam = fused_opt[0].fused_adam(p, fused_opt[1])
         fed = fed_tail if (adam is not None and fed_tail is not None) else None
         self._step(x, p, yy, ww, K, B, loss, correct, grad, expz, noise, keys, step, adam=adam, dbg=dbg,
-                   shared_frags=shared_frags, fed=fed)
+                   shared_frags=shared_frags, fed=fed, psi0=psi0)
         res = {"loss": loss, "grad": grad, "correct": correct, "expz": expz.reshape(K, B, self.C)}
         if adam is not None:
             res["opt_done"] = True

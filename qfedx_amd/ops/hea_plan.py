@@ -87,7 +87,8 @@ def frame_rows(k: int, n: int) -> list:
 
 @dataclass
 class Group:
-    layer: int                 # 1 = closed-form layer (gradient only), >= 2 rotation layer
+    layer: int                 # 1 = closed-form layer (gradient only; a rotation layer in amplitude plans), >= 2
+                               # rotation layer
     qubits: list               # logical qubits (<= 4)
     frame: int                 # CNOT chains before this layer
     slot: int = -1             # unitary fragment slot (rotation groups)
@@ -162,6 +163,17 @@ class HEAPlan:
     def n_theta(self) -> int:
         return 2 * self.n * self.L
 
+    @property
+    def amplitude(self) -> bool:
+        """The plan starts from stored (amplitude-encoded) states: layer 1 is an ordinary rotation layer, no pass
+        generates a product state and none carries layer-1 gradient groups (``build_plan(feature="amplitude")``)."""
+        return self.feature.lower() == "amplitude"
+
+    @property
+    def first_layer(self) -> int:
+        """First layer whose rotations run as group ops."""
+        return 1 if self.amplitude else 2
+
     def layer_frame(self, layer: int) -> int:
         return (layer - 1) if self.chain else 0
 
@@ -181,6 +193,14 @@ def eligible(spec) -> bool:
             and spec.n_qubits <= 30 and spec.n_classes <= MAX_CLASSES)
 
 
+def eligible_amplitude(spec) -> bool:
+    """Amplitude-encoded circuits this engine covers when asked for explicitly (``state_dtype: mfma | fp16 |
+    mfma_bf16``): RX/RZ layers from layer 1 on over a staged input state (csrc/hea_amp.hip), chain (or no) entangler,
+    no gate noise.  ``eligible`` stays False for them: ``auto`` keeps amplitude inputs on the fp32 VALU engine."""
+    return (spec.amplitude and not spec.noisy and spec.entangler in ("chain", "none") and spec.n_qubits >= 8
+            and spec.n_qubits <= 30 and spec.n_classes <= MAX_CLASSES)
+
+
 _PLAN_CACHE: dict = {}
 
 
@@ -189,16 +209,22 @@ def build_plan(n: int, L: int, readout, chain: bool = True, feature: str = "ry",
     """Plan the passes.  ``trim=None`` builds both the greedy plan (every ready rotation joins the current
     pass) and the trimmed plan (a non-final pass defers each layer's ragged tail so its groups are full
     4-qubit unitaries) and keeps the one with fewer passes, then fewer group ops: for 16q x 3L the trimmed
-    plan runs 8 group ops instead of 10 in the same two passes."""
+    plan runs 8 group ops instead of 10 in the same two passes.
+
+    ``feature="amplitude"``: the circuit starts from a stored state instead of a product state, so layer 1 is planned
+    as a rotation layer (frame 0, supports e_q), no pass gets layer-1 gradient groups and no coverage passes are
+    added: every theta slot lies in exactly one rotation group."""
     key = (n, L, tuple(readout), chain, feature, tile_bits, swizzle)
     if trim is None and key in _PLAN_CACHE:          # the candidate search runs once per circuit shape
         return copy.deepcopy(_PLAN_CACHE[key])
+    amp = feature.lower() == "amplitude"
+    first = 1 if amp else 2                      # first layer planned as rotation groups
     if trim is None:
         # candidates: no trimming, trimming everywhere, and per-layer trimming of the first (product-state)
         # pass with the later passes greedy or trimmed; ties keep the earlier candidate
         opts = [False, True]
-        for m in range(1, 1 << max(L - 1, 0)):
-            opts += [(m << 2,), (m << 2, -1)]
+        for m in range(1, 1 << max(L + 1 - first, 0)):
+            opts += [(m << first,), (m << first, -1)]
         cands = []
         for tr in opts:
             try:
@@ -216,12 +242,12 @@ def build_plan(n: int, L: int, readout, chain: bool = True, feature: str = "ry",
         raise ValueError("the MFMA engine needs at least 8 tile qubits (16 columns per MFMA block)")
     frame = (lambda layer: layer - 1) if chain else (lambda layer: 0)
     sup = {}
-    for layer in range(2, L + 1):
+    for layer in range(first, L + 1):
         for q in range(n):
             sup[(layer, q)] = frame_vec(q, frame(layer), n)
     preds = {}
     for (layer, q), s in sup.items():
-        preds[(layer, q)] = [(layer - 1, p) for p in range(n) if layer > 2 and (sup[(layer - 1, p)] & s)]
+        preds[(layer, q)] = [(layer - 1, p) for p in range(n) if layer > first and (sup[(layer - 1, p)] & s)]
     remaining = sorted(sup, key=lambda o: (o[0], o[1]))
     done = set()
     passes = []
@@ -270,7 +296,7 @@ def build_plan(n: int, L: int, readout, chain: bool = True, feature: str = "ry",
         if len(passes) > 16:
             raise RuntimeError("pass planner did not converge")
     # every qubit's bit must sit in some tile (layer-1 gradients): add group-free passes for the rest
-    covered = 0
+    covered = (1 << n) - 1 if amp else 0        # (amplitude plans: layer 1 is in the rotation groups)
     for p in passes:
         covered |= p.mask()
     while covered != (1 << n) - 1:
@@ -280,15 +306,15 @@ def build_plan(n: int, L: int, readout, chain: bool = True, feature: str = "ry",
         p = Pass(t - (min(n, lo + t - MIN_CONTIG) - lo), lo, min(n, lo + t - MIN_CONTIG))
         passes.append(p)
         covered |= p.mask()
-    # layer-1 gradient groups: first pass whose tile holds the qubit's bit
+    # layer-1 gradient groups: first pass whose tile holds the qubit's bit (none in an amplitude plan)
     owner = {}
-    for q in range(n):
+    for q in range(0 if amp else n):
         for j, p in enumerate(passes):
             if (p.mask() >> q) & 1:
                 owner[q] = j
                 break
     for j, p in enumerate(passes):
-        qs = [q for q in range(n) if owner[q] == j]
+        qs = [q for q in owner if owner[q] == j]
         for i in range(0, len(qs), GROUP):
             p.l1.append(Group(1, qs[i:i + GROUP], 0))
     slot = 0
@@ -906,17 +932,45 @@ def _round_bf16(z):
     return _bf16(z.real) + 1j * _bf16(z.imag)
 
 
+def amp_stage_ref(x: np.ndarray, n: int, storage: str = "fp16") -> np.ndarray:
+    """Numpy reference of the staging kernel (csrc/hea_amp.hip): raw features x [S, F <= 2^n] -> the real parts
+    [S, 2^n] (float64 values of the storage format; the imaginary halves are 0) it writes for forward pass 0.
+    Zero padding, float64 norm, a row whose norm is not > 0 -> the uniform state, fp32 quotient, the exact scale
+    2^(n // 2), one rounding to fp16 / bf16."""
+    x = np.asarray(x, dtype=np.float32)
+    S, F = x.shape
+    N = 1 << n
+    if F > N:
+        raise ValueError("more features than amplitudes")
+    xd = x.astype(np.float64)
+    nrm2 = (xd * xd).sum(1)
+    a = np.zeros((S, N), dtype=np.float32)
+    for s in range(S):
+        if nrm2[s] > 0.0:
+            a[s, :F] = (xd[s] * (1.0 / np.sqrt(nrm2[s]))).astype(np.float32)
+        else:
+            a[s] = np.float32(1.0 / np.sqrt(float(N)))
+    a = a * np.float32(1 << (n // 2))
+    if storage == "bf16":
+        return _bf16(a)
+    return a.astype(np.float16).astype(np.float64)
+
+
 def emulate(plan: HEAPlan, xang: np.ndarray, params: np.ndarray, wread=None, fp16: bool = False,
-            storage: str | None = None):
+            storage: str | None = None, init=None):
     """Tile-exact execution of ``plan`` with the kernel's tables.
 
     xang [K, B, n] encoded feature angles, params [K, P] (theta first), wread [K, B, C] = dL/d<Z_c>.
     Returns expz [K, B, C] and (if wread is given) theta gradients [K, n_theta] summed over samples.
     ``fp16`` rounds the stored amplitudes to half precision after every op (kernel storage format);
     ``storage="bf16"`` to bf16 instead (the bf16 build, csrc/hea_mfma_bf16.hip).
+    ``init`` [K, B, 2^n] real or complex, normalised: the input states of an amplitude plan (``xang`` is then unused);
+    they are scaled by 2^(n // 2) and rounded once to the storage format, as the staging kernel stores them.
     """
     n, t = plan.n, plan.t
-    K, B, _ = xang.shape
+    if plan.amplitude != (init is not None):
+        raise ValueError("amplitude plans start from init states, angle plans from feature angles")
+    K, B = (init.shape[:2] if plan.amplitude else xang.shape[:2])
     progs = pass_programs(plan)
     if storage is None:
         storage = "fp16" if fp16 else "exact"
@@ -932,12 +986,15 @@ def emulate(plan: HEAPlan, xang: np.ndarray, params: np.ndarray, wread=None, fp1
                 w = group_table(plan, p, g, OP_APPLY)
                 Us[g.slot] = group_unitary(th, len(g.qubits), w[W_TH:W_TH + 4], w[W_PH:W_PH + 4])
         for b in range(B):
-            wv = [rot_u(th[plan.theta_slot(1, q)], th[plan.theta_slot(1, q) + 1]) @ feature_vec(xang[k, b, q], plan.feature)
-                  for q in range(n)]
-            idx = np.arange(1 << n)
-            psi0 = np.full(1 << n, scale, dtype=np.complex128)
-            for q in range(n):
-                psi0 = psi0 * np.array(wv[q])[(idx >> q) & 1]
+            if plan.amplitude:
+                psi0 = np.asarray(init[k, b]).astype(np.complex128) * scale
+            else:
+                wv = [rot_u(th[plan.theta_slot(1, q)], th[plan.theta_slot(1, q) + 1]) @ feature_vec(xang[k, b, q], plan.feature)
+                      for q in range(n)]
+                idx = np.arange(1 << n)
+                psi0 = np.full(1 << n, scale, dtype=np.complex128)
+                for q in range(n):
+                    psi0 = psi0 * np.array(wv[q])[(idx >> q) & 1]
             psi0 = rnd(psi0)
             stored = [psi0]
             # forward passes
