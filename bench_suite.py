@@ -79,6 +79,12 @@ SUITE = {
                           "client local-steps/sec (10-qubit amplitude-encoded VQC x 64 clients, fp16 MFMA engine)", None),
     "vqc10q_amp64": ("configs/digits_amplitude_10q.yaml", ["model.state_dtype=fp32"],
                      "client local-steps/sec (10-qubit amplitude-encoded VQC x 64 clients)", None),
+    # the headline shape with a ring entangler: the MFMA engine (ring frames, three passes) against the fp32 VALU
+    # engine, which auto routing keeps for ring circuits
+    "vqc16q_ring64_mfma": ("configs/ring_16q_64clients.yaml", [],
+                           "client local-steps/sec (16-qubit ring-entangler VQC x 64 clients, fp16 MFMA engine)", None),
+    "vqc16q_ring64": ("configs/ring_16q_64clients.yaml", ["model.state_dtype=fp32"],
+                      "client local-steps/sec (16-qubit ring-entangler VQC x 64 clients)", None),
     "vqc4q_2_cpu": ("configs/baseline1_4q_2clients_cpu.yaml", ["train.local_steps=1"],
                     "client local-steps/sec (4-qubit VQC x 2 clients, CPU gloo)", None),
 }

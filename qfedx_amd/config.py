@@ -50,7 +50,9 @@ class ModelConfig:
                                         # hardware-efficient ansatz) | bf16 (bf16 MFMA engine when eligible, else
                                         # bf16 storage on the VALU pass engine) | bf16_valu.  feature_map: amplitude
                                         # stays on the VALU engine under auto / bf16; mfma | fp16 | mfma_bf16 run it
-                                        # on the MFMA engine (staged input states, >= 8 qubits)
+                                        # on the MFMA engine (staged input states, >= 8 qubits).  entangler: ring
+                                        # likewise: VALU engine under auto / bf16, MFMA engine (ring frames, angle
+                                        # features, 8..30 qubits, no gate noise) under mfma | fp16 | mfma_bf16
     simulator: str = "statevector"      # statevector | mps (tensor network past statevector memory) | density
                                         # (exact Kraus channels, <= 10 qubits; auto for noise.kind=amplitude)
     mps_chi: int = 64                   # MPS bond-dimension cap (exact while the circuit's bound fits)

@@ -23,7 +23,11 @@ def resolve_state_dtype(state_dtype: str, spec, backend: str, noise) -> str:
     Amplitude-encoded specs stay on the VALU engine under ``auto`` and ``bf16`` (``auto`` would otherwise trade fp32
     states for fp16 ones silently, and which engine is faster at 8-12 qubits depends on the shape); the explicit
     values ``mfma`` / ``fp16`` / ``mfma_bf16`` are passed through and run them on the MFMA engine when
-    ``hea_plan.eligible_amplitude`` holds (chain or no entangler, no gate noise, 8..30 qubits, <= 8 classes)."""
+    ``hea_plan.eligible_amplitude`` holds (chain or no entangler, no gate noise, 8..30 qubits, <= 8 classes).
+    Ring-entangler specs are routed the same way: VALU engine under ``auto`` / ``bf16``, MFMA engine under the explicit
+    values when ``hea_plan.eligible_ring`` holds (angle features); a ring spec outside it (gate noise, amplitude
+    features, qubit or class count) fails in
+    ``HeaMfmaProgram`` with the reason (``hea_plan.refusal``)."""
     if state_dtype == "bf16_valu":
         return "bf16"
     if state_dtype == "bf16":

@@ -311,7 +311,7 @@ class VQCEngine:
             elif method == "param_shift":
                 # shifted expectations carry the readout channel themselves: w = dL/d<Z>_noisy unscaled
                 if (self.backend == "hip" and hasattr(self.hip, "param_shift") and init is None
-                        and self.ps_reuse):
+                        and self.ps_reuse and not getattr(self.hip, "ring", False)):
                     # MFMA engine: prefix reuse + the pi identity (same estimator, ~2.5x fewer pass launches)
                     nz = self.noise if (self.noise is not None and self.noise.readout_noise) else None
                     gth = self.hip.param_shift(xang, params, w, nz, readout_keys, step)

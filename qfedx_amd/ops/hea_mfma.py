@@ -15,7 +15,8 @@ It exposes the subset of ``HipProgram``'s interface the engine / trainer use (``
 swaps it in for circuits ``hea_plan.eligible`` accepts.  Amplitude-encoded circuits (``hea_plan.eligible_amplitude``)
 run too: real ``init`` rows are normalised and written in the storage format by ``hea_amp_stage`` (csrc/hea_amp.hip),
 forward pass 0 loads that buffer instead of generating a product state, and layer 1 is an ordinary rotation layer of
-the plan.  Amplitudes are stored as fp16 scaled by
+the plan.  Ring-entangler circuits (``hea_plan.eligible_ring``) run on ring plans (``build_plan(ring=True)``): the same
+kernels, other tables.  Amplitudes are stored as fp16 scaled by
 2^(n/2) (unit-magnitude typical values); MFMAs accumulate in fp32 and the unitaries carry a hi/lo fp16
 split, so the only rounding is the fp16 state between ops (~2^-12 relative per op).
 """
@@ -29,7 +30,7 @@ import torch
 
 from ._ext import ext
 from .hea_plan import (OP_APPLY, OP_APPLY2, OP_BACK, OP_BACK2, OP_GRAD2, OP_GRAD_L1, OP_READOUT, TILE_BITS, W_CODE, build_plan, eligible,
-                       eligible_amplitude, fo_table, obs_table, pass_programs)
+                       eligible_amplitude, eligible_ring, fo_table, obs_table, pass_programs, refusal, widen_plan)
 
 ADJ_TILE_BITS = 13   # adjoint tiles: 2^13 amplitudes x (psi, lambda) = 64 KB of LDS -> two workgroups per CU
 
@@ -87,6 +88,14 @@ def obs_load_default() -> bool:
     return os.environ.get("QFEDX_HEA_OBS_LOAD", "1" if OBS_LOAD_DEFAULT else "0") != "0"
 
 
+def ring_fwd_from_adj() -> bool:
+    """``QFEDX_HEA_RING_ADJ`` = 13 / 14: a ring program's forward runs the groups of its 2^13-tile plan on widened
+    tiles, so the adjoint runs on 2^13 tiles (two workgroups per CU) / the forward runs its own 2^14 plan (fewer group
+    ops) and the adjoint runs on the same 2^14 tiles.  Default ``RING_FWD_FROM_ADJ``."""
+    env = os.environ.get("QFEDX_HEA_RING_ADJ", "")
+    return RING_FWD_FROM_ADJ if env == "" else env == "13"
+
+
 _SPEC_WARNED = False
 _NO_KEYS = torch.zeros(0, dtype=torch.int64)
 _NODBG = torch.zeros(0, dtype=torch.int64)     # no stall-attribution buffer (stamps build only)
@@ -106,6 +115,12 @@ SPLIT_READOUT_MIN_SAMPLES = 128
 # knob-1 run below every parent run; 8 clients 0.255 -> 0.250, inside three spreads (0.016): a tie.  Compiled into the
 # one kernel a pass has, so not gated by sample count.
 OBS_LOAD_DEFAULT = True
+# Ring programs: forward on the 2^13 plan's grouping with a 2^13 adjoint (True) or native 2^14 groups with a 2^14
+# adjoint (False); 16q x 3L: 9 against 8 group ops, both in 3 passes.  Measured, clients x 32 samples, ms per step,
+# alternating x 3 on one box (profiles/hea_ring_plan_ab.txt): 64 clients 2.070 -> 2.021 (every run below every native
+# run), 8 clients 0.339 -> 0.332: the pass with the layer-1 gradient groups gains more from two workgroups per CU
+# (0.52 -> 0.40 ms) than the extra group op costs the other passes.
+RING_FWD_FROM_ADJ = True
 
 
 class HeaMfmaProgram:
@@ -117,11 +132,15 @@ class HeaMfmaProgram:
             raise ValueError(f"MFMA engine storage must be fp16 | bf16, got {storage!r}")
         self.storage = storage
         self.bf16 = storage == "bf16"
-        if not (eligible(spec) or eligible_amplitude(spec)):
+        if not (eligible(spec) or eligible_amplitude(spec) or eligible_ring(spec)):
             raise ValueError("the MFMA engine covers angle-encoded (hea_plan.eligible) and amplitude-encoded "
-                             "(hea_plan.eligible_amplitude) RX/RZ + CNOT-chain VQCs with 8..30 qubits, no gate noise "
-                             "and <= 8 classes")
+                             "(hea_plan.eligible_amplitude) RX/RZ + CNOT-chain VQCs and angle-encoded ring-entangler "
+                             "ones (hea_plan.eligible_ring) with 8..30 qubits, no gate noise and <= 8 classes; refused: "
+                             + refusal(spec))
         self.spec = spec
+        # ring entangler: the plans' frames count ring layers (hea_plan.frame_vec(ring=True)); the kernels are table
+        # driven and run them unchanged
+        self.ring = spec.entangler == "ring"
         # amplitude program: forward pass 0 loads the staged input states (``_stage``) instead of generating the
         # layer-1 product state, and every layer's rotations are group ops
         self.amplitude = bool(spec.amplitude)
@@ -135,7 +154,7 @@ class HeaMfmaProgram:
             adj_tile_bits = int(os.environ.get("QFEDX_HEA_ADJ_TILE", min(tile_bits, ADJ_TILE_BITS)))
         self.tile_bits = tile_bits
         self.plan = build_plan(self.n, spec.n_layers, spec.readout, spec.entangler == "chain", spec.feature_map,
-                               tile_bits)
+                               tile_bits, ring=self.ring)
         # The adjoint may run on smaller tiles than the forward (2^13 amplitudes: two adjoint workgroups per
         # CU, one's tile load hidden behind the other's group ops) when that plan has the same passes, rotation
         # groups and unitary slots: pass outputs are stored in memory order, so the tiling of a pass is free to
@@ -143,9 +162,17 @@ class HeaMfmaProgram:
         plan_a = self.plan
         if adj_tile_bits != tile_bits:
             cand = build_plan(self.n, spec.n_layers, spec.readout, spec.entangler == "chain", spec.feature_map,
-                              adj_tile_bits)
+                              adj_tile_bits, ring=self.ring)
             if _same_passes(self.plan, cand):
                 plan_a = cand
+            elif (self.ring and ring_fwd_from_adj() and adj_tile_bits < tile_bits
+                  and len(cand.passes) <= len(self.plan.passes)):
+                # a ring's independently planned small-tile plan groups its rotations differently: run the forward on
+                # that plan's groups, each pass tile widened to the forward size (hea_plan.widen_plan)
+                self.plan = widen_plan(cand, tile_bits)
+                plan_a = cand
+                if not _same_passes(self.plan, plan_a):
+                    raise RuntimeError("the widened ring plan lost a group of its source plan")
         self.adj_plan = plan_a
         self.adj_tile_bits = plan_a.passes[0].t if plan_a.passes else tile_bits
         C = ext()
@@ -548,6 +575,9 @@ class HeaMfmaProgram:
         if self.amplitude:
             raise ValueError("prefix-reuse parameter shift is angle-only: an amplitude program's shifted circuits run "
                              "as parameter rows of expz(init=...) (VQCEngine.param_shift_batched)")
+        if self.ring:
+            raise ValueError("prefix-reuse parameter shift is chain-only: a ring program's shifted circuits run as "
+                             "parameter rows of expz (VQCEngine.param_shift_batched)")
         own = [[] for _ in range(self.fwd_last + 1)]
         for q in range(self.n):
             own[0] += [self.plan.theta_slot(1, q), self.plan.theta_slot(1, q) + 1]
@@ -676,6 +706,9 @@ class HeaMfmaProgram:
         if self.amplitude:
             raise ValueError("prefix-reuse parameter shift is angle-only: an amplitude program's shifted circuits run "
                              "as parameter rows of expz(init=...) (VQCEngine.param_shift_batched)")
+        if self.ring:
+            raise ValueError("prefix-reuse parameter shift is chain-only: a ring program's shifted circuits run as "
+                             "parameter rows of expz (VQCEngine.param_shift_batched)")
         K, B, C = w.shape
         P = self.n_theta
         noisy = noise is not None and not exact_only

@@ -27,6 +27,11 @@ GEMMs (MFMA, ``csrc/hea_mfma.hip``) instead of per-gate VALU sweeps:
   A layer-1 qubit's 2 x 2 cross matrix is measured in the first pass whose tile holds its bit (every
   earlier pass avoids that bit, and unitaries on other bits preserve the partial inner product).
 
+* **Ring entanglers.**  A ring layer is the linear map R = C P (P, then bit 0 flips when bit n-1 is set), so the
+  same frames cover it (``frame_vec`` / ``frame_rows`` with ``ring=True``) and the kernels, which only see tables,
+  run ring plans unchanged.  R is not triangular: ``_ring_plan`` orders rotations by the exact commutation rule
+  (``ring_rotations``) and keeps what does not commute with a not-yet-measured layer-1 rotation out of early passes.
+
 Everything here is host-side planning (runs once per circuit shape).  ``emulate`` executes a plan
 tile by tile with exactly the kernel's addressing tables in float64 numpy: it is the oracle the CPU
 tests hold against a dense simulation, and the HIP kernel is tested against both.
@@ -64,17 +69,43 @@ def parity(x: int) -> int:
     return bin(x).count("1") & 1
 
 
-def frame_vec(q: int, k: int, n: int) -> int:
-    """Memory mask P^-k e_q that a rotation on logical qubit q pairs after k CNOT chains."""
+def frame_vec(q: int, k: int, n: int, ring: bool = False) -> int:
+    """Memory mask P^-k e_q that a rotation on logical qubit q pairs after k CNOT chains.  ``ring``: after k ring
+    layers, R^-k e_q with R = C P, C the closing cx(n-1, 0) (``ring_step``): R^-1 v = P^-1 (C v)."""
     v = 1 << q
     full = (1 << n) - 1
     for _ in range(k):
+        if ring and (v >> (n - 1)) & 1:
+            v ^= 1
         v = (v ^ (v << 1)) & full
     return v
 
 
-def frame_rows(k: int, n: int) -> list:
-    """Row masks of P^k: logical bit q of memory index y is parity(y & R[q])."""
+def ring_step(y: int, n: int) -> int:
+    """One ring entangler layer on a basis index: y -> R y = C P y (prefix XOR, then bit 0 flips when bit n-1 is set:
+    the cx(n-1, 0) ``VQCSpec.circuit`` adds for n > 2)."""
+    acc = out = 0
+    for q in range(n):
+        acc ^= (y >> q) & 1
+        out |= acc << q
+    return out ^ 1 if (out >> (n - 1)) & 1 else out
+
+
+def _ring_rows(k: int, n: int) -> list:
+    """Row masks of R^k (from its columns R^k e_j).  Row 0 of R is dense (every bit >= 1): R is not triangular."""
+    cols = []
+    for j in range(n):
+        y = 1 << j
+        for _ in range(k):
+            y = ring_step(y, n)
+        cols.append(y)
+    return [sum(((cols[j] >> q) & 1) << j for j in range(n)) for q in range(n)]
+
+
+def frame_rows(k: int, n: int, ring: bool = False) -> list:
+    """Row masks of P^k (``ring``: of R^k): logical bit q of memory index y is parity(y & R[q])."""
+    if ring:
+        return _ring_rows(k, n)
     R = [1 << q for q in range(n)]
     for _ in range(k):
         acc, new = 0, []
@@ -92,9 +123,10 @@ class Group:
     qubits: list               # logical qubits (<= 4)
     frame: int                 # CNOT chains before this layer
     slot: int = -1             # unitary fragment slot (rotation groups)
+    ring: bool = False         # the frame counts ring layers (frame_vec / frame_rows with ring=True)
 
     def vecs(self, n):
-        return [frame_vec(q, self.frame, n) for q in self.qubits]
+        return [frame_vec(q, self.frame, n, self.ring) for q in self.qubits]
 
     def support(self, n):
         s = 0
@@ -158,6 +190,7 @@ class HEAPlan:
     t: int
     passes: list
     n_slots: int                 # rotation groups (unitary fragments per client)
+    ring: bool = False           # ring entangler (``chain`` is then False): frames count ring layers
 
     @property
     def n_theta(self) -> int:
@@ -175,11 +208,11 @@ class HEAPlan:
         return 1 if self.amplitude else 2
 
     def layer_frame(self, layer: int) -> int:
-        return (layer - 1) if self.chain else 0
+        return (layer - 1) if (self.chain or self.ring) else 0
 
     @property
     def obs_masks(self) -> list:
-        R = frame_rows(self.L if self.chain else 0, self.n)
+        R = frame_rows(self.L if (self.chain or self.ring) else 0, self.n, self.ring)
         return [R[q] for q in self.readout]
 
     def theta_slot(self, layer: int, q: int) -> int:
@@ -201,11 +234,42 @@ def eligible_amplitude(spec) -> bool:
             and spec.n_qubits <= 30 and spec.n_classes <= MAX_CLASSES)
 
 
+def eligible_ring(spec) -> bool:
+    """Ring-entangler circuits this engine covers when asked for explicitly (``state_dtype: mfma | fp16 | mfma_bf16``):
+    angle features, RX/RZ layers, no gate noise, 8..30 qubits (so n > 2: the ring is closed), <= 8 classes.
+    ``eligible`` stays False for them: ``auto`` / ``bf16`` keep ring circuits on the VALU engine.  Amplitude-encoded
+    ring circuits stay refused (the VALU engine runs them), although the planner and the emulator handle them
+    (``build_plan(feature="amplitude", ring=True)``)."""
+    return (spec.entangler == "ring" and not spec.noisy and not spec.amplitude
+            and spec.feature_map.lower() in ("rx", "ry", "rz")
+            and 8 <= spec.n_qubits <= 30 and spec.n_classes <= MAX_CLASSES)
+
+
+def refusal(spec) -> str:
+    """Why none of ``eligible`` / ``eligible_amplitude`` / ``eligible_ring`` holds for ``spec`` ('' if one does)."""
+    if eligible(spec) or eligible_amplitude(spec) or eligible_ring(spec):
+        return ""
+    why = []
+    if spec.noisy:
+        why.append("gate noise (Pauli trajectories) runs on the VALU engine only")
+    if not 8 <= spec.n_qubits <= 30:
+        why.append(f"{spec.n_qubits} qubits is outside 8..30")
+    if spec.n_classes > MAX_CLASSES:
+        why.append(f"{spec.n_classes} classes is more than {MAX_CLASSES}")
+    if spec.amplitude and spec.entangler == "ring":
+        why.append("amplitude features with a ring entangler run on the VALU engine only")
+    if spec.entangler not in ("chain", "none", "ring"):
+        why.append(f"entangler {spec.entangler!r} is not chain | ring | none")
+    if not spec.amplitude and spec.feature_map.lower() not in ("rx", "ry", "rz"):
+        why.append(f"feature map {spec.feature_map!r} is not rx | ry | rz | amplitude")
+    return "; ".join(why) or "unsupported circuit"
+
+
 _PLAN_CACHE: dict = {}
 
 
 def build_plan(n: int, L: int, readout, chain: bool = True, feature: str = "ry",
-               tile_bits: int = TILE_BITS, swizzle: bool = True, trim=None) -> HEAPlan:
+               tile_bits: int = TILE_BITS, swizzle: bool = True, trim=None, ring: bool = False) -> HEAPlan:
     """Plan the passes.  ``trim=None`` builds both the greedy plan (every ready rotation joins the current
     pass) and the trimmed plan (a non-final pass defers each layer's ragged tail so its groups are full
     4-qubit unitaries) and keeps the one with fewer passes, then fewer group ops: for 16q x 3L the trimmed
@@ -213,12 +277,24 @@ def build_plan(n: int, L: int, readout, chain: bool = True, feature: str = "ry",
 
     ``feature="amplitude"``: the circuit starts from a stored state instead of a product state, so layer 1 is planned
     as a rotation layer (frame 0, supports e_q), no pass gets layer-1 gradient groups and no coverage passes are
-    added: every theta slot lies in exactly one rotation group."""
+    added: every theta slot lies in exactly one rotation group.
+
+    ``ring=True`` (or ``chain="ring"``): a ring entangler.  Frames count ring layers (``frame_vec(..., ring=True)``),
+    dependencies are the exact commutation DAG and an angle plan keeps every rotation that does not commute with a
+    not-yet-measured layer-1 rotation out of the early passes (``_ring_plan``).  Chain / no-entangler plans do not go
+    through that code."""
+    if chain == "ring":
+        chain, ring = False, True
     key = (n, L, tuple(readout), chain, feature, tile_bits, swizzle)
+    if ring:
+        chain = False
+        key += ("ring",)
     if trim is None and key in _PLAN_CACHE:          # the candidate search runs once per circuit shape
         return copy.deepcopy(_PLAN_CACHE[key])
     amp = feature.lower() == "amplitude"
     first = 1 if amp else 2                      # first layer planned as rotation groups
+    if ring and n <= 2:
+        raise ValueError("a ring entangler needs more than 2 qubits (VQCSpec closes the ring for n > 2 only)")
     if trim is None:
         # candidates: no trimming, trimming everywhere, and per-layer trimming of the first (product-state)
         # pass with the later passes greedy or trimmed; ties keep the earlier candidate
@@ -228,7 +304,7 @@ def build_plan(n: int, L: int, readout, chain: bool = True, feature: str = "ry",
         cands = []
         for tr in opts:
             try:
-                cands.append(build_plan(n, L, readout, chain, feature, tile_bits, False, tr))
+                cands.append(build_plan(n, L, readout, chain, feature, tile_bits, False, tr, ring))
             except RuntimeError:
                 continue
         best = min(cands, key=lambda pl: (len(pl.passes), sum(len(p.groups) for p in pl.passes)))
@@ -237,6 +313,12 @@ def build_plan(n: int, L: int, readout, chain: bool = True, feature: str = "ry",
                 layout_pass(best, p, seed=j)
         _PLAN_CACHE[key] = copy.deepcopy(best)
         return best
+    if ring:
+        plan = _ring_plan(n, L, readout, feature, tile_bits, trim)
+        if swizzle:
+            for j, p in enumerate(plan.passes):
+                layout_pass(plan, p, seed=j)
+        return plan
     t = min(tile_bits, n)
     if t < GROUP + 4:
         raise ValueError("the MFMA engine needs at least 8 tile qubits (16 columns per MFMA block)")
@@ -355,6 +437,161 @@ def _trim_ragged(taken: list, preds: dict, layers: int = -1) -> list:
         keep = [o for o in keep if o not in drop]
 
 
+def _assign_l1(passes: list, n: int, amp: bool) -> None:
+    """Layer-1 gradient groups: first pass whose tile holds the qubit's bit (none in an amplitude plan)."""
+    owner = {}
+    for q in range(0 if amp else n):
+        for j, p in enumerate(passes):
+            if (p.mask() >> q) & 1:
+                owner[q] = j
+                break
+    for j, p in enumerate(passes):
+        qs = [q for q in owner if owner[q] == j]
+        p.l1 = [Group(1, qs[i:i + GROUP], 0) for i in range(0, len(qs), GROUP)]
+
+
+def ring_rotations(n: int, L: int, first: int) -> tuple:
+    """Per rotation (layer, q) of a ring circuit its memory vector u = R^-(l-1) e_q and row mask r = row q of R^(l-1),
+    and ``preds``: every rotation of an earlier layer it does not commute with.  Rotations a, b of different layers
+    commute iff parity(u_a & r_b) = parity(u_b & r_a) = 0 (a is generated by the shift X_u_a and the sign Z_r_a, and
+    X_u Z_r = (-1)^(u . r) Z_r X_u); rotations of one layer always commute.  R is not triangular, so a rotation can
+    depend on rotations more than one layer below: (l, 0) on every (l-1, p >= 1), and every (l+1, .) on (l, 0)."""
+    u, r = {}, {}
+    for layer in range(first, L + 1):
+        rows = frame_rows(layer - 1, n, True)
+        for q in range(n):
+            u[(layer, q)] = frame_vec(q, layer - 1, n, True)
+            r[(layer, q)] = rows[q]
+    preds = {o: [a for a in u if a[0] < o[0] and (parity(u[a] & r[o]) or parity(u[o] & r[a]))] for o in u}
+    return u, r, preds
+
+
+def _ring_plan(n: int, L: int, readout, feature: str, tile_bits: int, trim) -> HEAPlan:
+    """One ring plan (no swizzle) for a trim option of ``build_plan``.  Pass 0 is the low t bits (it generates the
+    product state or loads the staged input); every later pass takes the tile (c low bits from the minimum contiguous
+    run up to t, a window anywhere above) that admits the most rotations, ties broken by newly covered bits.  A
+    rotation joins a pass when its vector lies in the tile, every non-commuting rotation of an earlier layer is done
+    (``ring_rotations``: the exact DAG) and - angle plans - it commutes with the layer-1 rotation (u = r = e_q) of every
+    qubit q no tile has covered yet: q's 2 x 2 cross matrix is measured at the input of the first pass whose tile
+    holds bit q, which is only the layer-1 gradient if everything run before commutes with it."""
+    amp = feature.lower() == "amplitude"
+    first = 1 if amp else 2
+    t = min(tile_bits, n)
+    if t < GROUP + 4:
+        raise ValueError("the MFMA engine needs at least 8 tile qubits (16 columns per MFMA block)")
+    full = (1 << n) - 1
+    u, r, preds = ring_rotations(n, L, first)
+    remaining = sorted(u)
+    done = set()
+    passes = []
+    covered = full if amp else 0
+
+    def admit(p):
+        tm = p.mask()
+        open_bits = full & ~(covered | tm)           # layer-1 qubits measured in a later pass
+        taken, have = [], set(done)
+        for o in remaining:
+            ok = (u[o] & ~tm) == 0 and not ((u[o] | r[o]) & open_bits)
+            if ok and all(d in have for d in preds[o]):
+                taken.append(o)
+                have.add(o)
+        return taken
+
+    while remaining:
+        if not passes:
+            p = Pass(t, t, t)
+            taken = admit(p)
+        else:
+            mc = min(MIN_CONTIG, max(2, t - 6))
+            best = None
+            for c in range(t, mc - 1, -1):          # (ties keep the longer contiguous run)
+                w = t - c
+                for lo in ([c] if w == 0 else range(c + 1, n - w + 1)):
+                    cand = Pass(c, lo, lo + w)
+                    tk = admit(cand)
+                    score = (len(tk), bin(cand.mask() & ~covered).count("1"))
+                    if best is None or score > best[0]:
+                        best = (score, cand, tk)
+            score, p, taken = best
+            if score == (0, 0):
+                raise RuntimeError(f"ring pass planner stuck at {len(passes)} passes (n={n}, L={L}, t={t})")
+        if isinstance(trim, tuple):         # per-pass layer masks (bit l = trim layer l; -1 = all layers)
+            j = len(passes)
+            layers = trim[j] if j < len(trim) else (-1 if trim[-1] == -1 else 0)
+        else:
+            layers = -1 if trim else 0
+        if layers and taken and len(taken) < len(remaining):
+            taken = _trim_ragged(taken, preds, layers)
+        done.update(taken)
+        remaining = [o for o in remaining if o not in done]
+        by_layer = {}
+        for (layer, q) in taken:
+            by_layer.setdefault(layer, []).append(q)
+        for layer in sorted(by_layer):
+            qs = sorted(by_layer[layer])
+            for i in range(0, len(qs), GROUP):
+                p.groups.append(Group(layer, qs[i:i + GROUP], layer - 1, ring=True))
+        covered |= p.mask()
+        passes.append(p)
+        if len(passes) > 16:
+            raise RuntimeError("ring pass planner did not converge")
+    while covered != full:                  # (angle plans) group-free passes for bits no tile holds yet
+        top = full & ~covered
+        lo = max(top.bit_length() - (t - MIN_CONTIG), min(b for b in range(n) if (top >> b) & 1))
+        lo = max(lo, MIN_CONTIG)
+        p = Pass(t - (min(n, lo + t - MIN_CONTIG) - lo), lo, min(n, lo + t - MIN_CONTIG))
+        passes.append(p)
+        covered |= p.mask()
+    _assign_l1(passes, n, amp)
+    slot = 0
+    for p in passes:
+        for g in p.groups:
+            g.slot = slot
+            slot += 1
+    return HEAPlan(n, L, len(readout), list(readout), False, feature, t, passes, slot, ring=True)
+
+
+def widen_plan(plan: HEAPlan, tile_bits: int, swizzle: bool = True) -> HEAPlan:
+    """The plan with the same rotation groups (and slots) per pass as ``plan`` on tiles of ``tile_bits`` bits: every
+    pass tile is widened (low run first, then the window downwards, then upwards), so each group's support stays
+    inside it.  Layer-1 gradient groups are reassigned to the first tile holding their bit: tiles only grow, so every
+    bit is covered no later than before and the layer-1 commutation rule keeps holding.  ``HeaMfmaProgram`` runs a ring
+    forward on this (2^14 tiles) over a 2^13 adjoint plan: the two then have the same passes by construction."""
+    n = plan.n
+    t = min(tile_bits, n)
+    key = ("widen", n, plan.L, tuple(plan.readout), plan.chain, plan.ring, plan.feature, tile_bits, swizzle,
+           tuple((p.c, p.lo, p.hi, tuple((g.layer, tuple(g.qubits), g.frame, g.slot) for g in p.groups))
+                 for p in plan.passes))
+    if key in _PLAN_CACHE:                  # (the layout search below runs once per source plan)
+        return copy.deepcopy(_PLAN_CACHE[key])
+    passes = []
+    for p in plan.passes:
+        c, lo, hi = p.c, p.lo, p.hi
+        while c + hi - lo < t:
+            if hi == lo:                    # a contiguous low tile
+                c, lo, hi = c + 1, c + 1, c + 1
+            elif c < lo:
+                c += 1
+            elif hi < n:
+                hi += 1
+            else:
+                raise RuntimeError("cannot widen a pass tile")
+        if c == lo:                         # the window touches the low run: one contiguous tile [0, hi)
+            c, lo, hi = hi, hi, hi
+        q = Pass(c, lo, hi, groups=copy.deepcopy(p.groups))
+        if q.mask() & p.mask() != p.mask():
+            raise RuntimeError("a widened tile lost bits")
+        passes.append(q)
+    _assign_l1(passes, n, plan.amplitude)
+    out = HEAPlan(n, plan.L, plan.C, list(plan.readout), plan.chain, plan.feature, t, passes, plan.n_slots,
+                  ring=plan.ring)
+    if swizzle:
+        for j, p in enumerate(passes):
+            layout_pass(out, p, seed=j)
+    _PLAN_CACHE[key] = copy.deepcopy(out)
+    return out
+
+
 # ---------------------------------------------------------------------------------------- op tables
 def _neutral_pads(vt: list, rt: list, t: int, need: int) -> list:
     """``need`` tile vectors independent of ``vt`` whose logical parity against every ``rt`` mask is 0."""
@@ -456,7 +693,7 @@ def _rank(vals) -> int:
 def _group_geom(plan: HEAPlan, p: Pass, g: Group):
     """Tile-local group vectors (padded to 4), row masks, non-pivot bits and their column directions."""
     n, t = plan.n, p.t
-    R = frame_rows(g.frame, n)
+    R = frame_rows(g.frame, n, g.ring)
     vt = [p.to_tile(v) for v in g.vecs(n)]
     for v, vm in zip(vt, g.vecs(n)):
         if p.to_tile(vm) != v or (vm & ~p.mask()):

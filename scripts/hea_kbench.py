@@ -22,6 +22,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--spec", type=int, choices=(0, 1), default=None,
                     help="1: per-plan pass kernels, 0: the interpreter (default: QFEDX_HEA_SPEC)")
+    ap.add_argument("--entangler", choices=("chain", "ring", "none"), default="chain",
+                    help="ring: QFEDX_HEA_RING_ADJ=13 | 14 selects the adjoint tiling (profiles/hea_ring_plan_ab.txt)")
     ap.add_argument("--precision", action="store_true", help="also report errors against the fp32 VALU engine")
     args = ap.parse_args()
     import torch
@@ -30,7 +32,7 @@ def main():
     from qfedx_amd.ops.hea_mfma import _NODBG, HeaMfmaProgram
 
     dev = torch.device("cuda", 0)
-    spec = VQCSpec(args.qubits, args.layers, 3)
+    spec = VQCSpec(args.qubits, args.layers, 3, entangler=args.entangler)
     prog = HeaMfmaProgram(spec, dev, use_spec=None if args.spec is None else bool(args.spec))
     sf, sa = getattr(prog, "spec_fwd", None), getattr(prog, "spec_adj", None)   # (older trees: no per-plan kernels)
     K, B = args.clients, args.batch
@@ -63,7 +65,9 @@ def main():
     fempty = torch.empty(0, dtype=torch.float32, device=dev)
     J = prog.n_passes
     N = S << prog.n
-    res = {"step_ms": round(step_ms, 4), "n_passes": J, "samples": S, "spec": bool(getattr(prog, "spec_active", False)),
+    res = {"step_ms": round(step_ms, 4), "n_passes": J, "samples": S, "entangler": args.entangler,
+           "tile_bits": [prog.plan.t, getattr(prog, "adj_tile_bits", None)], "group_ops": prog.plan.n_slots,
+           "spec": bool(getattr(prog, "spec_active", False)),
            # per pass: does a training step launch the per-plan kernel (the timed step_ms) - the per-pass lines below
            # launch a pass's per-plan kernel whenever it has one
            "spec_passes": (prog.spec_passes(samples=S) if hasattr(prog, "readout_mode") else
