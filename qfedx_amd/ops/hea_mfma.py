@@ -29,19 +29,10 @@ import numpy as np
 import torch
 
 from ._ext import ext
-from .hea_plan import (OP_APPLY, OP_APPLY2, OP_BACK, OP_BACK2, OP_GRAD2, OP_GRAD_L1, OP_READOUT, TILE_BITS, W_CODE, build_plan, eligible,
-                       eligible_amplitude, eligible_ring, fo_table, obs_table, pass_programs, refusal, widen_plan)
+from .hea_plan import (OP_APPLY, OP_APPLY2, OP_BACK, OP_BACK2, OP_GRAD2, OP_GRAD_L1, OP_READOUT, TILE_BITS, W_CODE, eligible,
+                       eligible_amplitude, eligible_ring, fo_table, obs_table, pass_programs, plan_pair, refusal)
 
 ADJ_TILE_BITS = 13   # adjoint tiles: 2^13 amplitudes x (psi, lambda) = 64 KB of LDS -> two workgroups per CU
-
-
-def _same_passes(a, b) -> bool:
-    """Two plans run the same rotation groups (and unitary slots) in the same passes - only their tile geometry
-    differs.  The layer-1 gradient groups may sit in other passes: they exist only in the adjoint programs
-    (the forward generates the whole layer-1 product state in its first pass)."""
-    def sig(plan):
-        return [sorted((g.slot, g.layer, tuple(g.qubits), g.frame) for g in p.groups) for p in plan.passes]
-    return a.n_slots == b.n_slots and sig(a) == sig(b)
 
 _FEATURE = {"ry": 0, "rx": 1, "rz": 2, "amplitude": 0}      # (an amplitude program never generates: unused)
 
@@ -153,26 +144,9 @@ class HeaMfmaProgram:
         if adj_tile_bits is None:
             adj_tile_bits = int(os.environ.get("QFEDX_HEA_ADJ_TILE", min(tile_bits, ADJ_TILE_BITS)))
         self.tile_bits = tile_bits
-        self.plan = build_plan(self.n, spec.n_layers, spec.readout, spec.entangler == "chain", spec.feature_map,
-                               tile_bits, ring=self.ring)
-        # The adjoint may run on smaller tiles than the forward (2^13 amplitudes: two adjoint workgroups per
-        # CU, one's tile load hidden behind the other's group ops) when that plan has the same passes, rotation
-        # groups and unitary slots: pass outputs are stored in memory order, so the tiling of a pass is free to
-        # differ.
-        plan_a = self.plan
-        if adj_tile_bits != tile_bits:
-            cand = build_plan(self.n, spec.n_layers, spec.readout, spec.entangler == "chain", spec.feature_map,
-                              adj_tile_bits, ring=self.ring)
-            if _same_passes(self.plan, cand):
-                plan_a = cand
-            elif (self.ring and ring_fwd_from_adj() and adj_tile_bits < tile_bits
-                  and len(cand.passes) <= len(self.plan.passes)):
-                # a ring's independently planned small-tile plan groups its rotations differently: run the forward on
-                # that plan's groups, each pass tile widened to the forward size (hea_plan.widen_plan)
-                self.plan = widen_plan(cand, tile_bits)
-                plan_a = cand
-                if not _same_passes(self.plan, plan_a):
-                    raise RuntimeError("the widened ring plan lost a group of its source plan")
+        # the adjoint runs on its own (smaller) tiles where a plan with the forward's passes exists: hea_plan.plan_pair
+        self.plan, plan_a = plan_pair(self.n, spec.n_layers, spec.readout, spec.entangler, spec.feature_map, tile_bits,
+                                      adj_tile_bits, ring_fwd_from_adj())
         self.adj_plan = plan_a
         self.adj_tile_bits = plan_a.passes[0].t if plan_a.passes else tile_bits
         C = ext()
@@ -522,14 +496,27 @@ class HeaMfmaProgram:
             raise ValueError("one parameter row per client expected")
         return x, p, K, B
 
+    def _pad_params(self, th: torch.Tensor) -> torch.Tensor:
+        """Theta-only parameter rows zero-padded to the kernels' param stride (n_theta + the 2 C readout affines)."""
+        short = self.n_theta + 2 * self.C - th.shape[1]
+        return torch.cat([th, th.new_zeros(th.shape[0], short)], 1) if short > 0 else th
+
+    def _need_prefix_reuse(self) -> None:
+        """Prefix reuse starts shifted circuits from the chain forward's stored pass outputs and layer-1 product state."""
+        if self.amplitude:
+            raise ValueError("prefix-reuse parameter shift is angle-only: an amplitude program's shifted circuits run "
+                             "as parameter rows of expz(init=...) (VQCEngine.param_shift_batched)")
+        if self.ring:
+            raise ValueError("prefix-reuse parameter shift is chain-only: a ring program's shifted circuits run as "
+                             "parameter rows of expz (VQCEngine.param_shift_batched)")
+
     # ------------------------------------------------------------------ forward / eval
     @torch.no_grad()
     def expz(self, xang: torch.Tensor, theta: torch.Tensor, noise=None, keys=None, step: int = 0,
              init: torch.Tensor | None = None) -> torch.Tensor:
         x, th, K, B = self._prep(xang, theta)
         self._check_init(init)
-        if th.shape[1] < self.n_theta + 2 * self.C:    # pad theta-only rows to the kernel's param stride
-            th = torch.cat([th, th.new_zeros(K, self.n_theta + 2 * self.C - th.shape[1])], 1)
+        th = self._pad_params(th)
         S = K * B
         out = self._buf("expz", S * self.C, torch.float32)
         # clients per launch: two live states per sample fit the HBM budget (24q: 128 MiB per sample)
@@ -553,8 +540,7 @@ class HeaMfmaProgram:
         """Adjoint VJP of sum_c w[s, c] <Z_c>_s -> (<Z> [S, C], d/dtheta [K, n_theta])."""
         x, th, K, B = self._prep(xang, theta)
         psi0 = self._start(init, K, B)
-        if th.shape[1] < self.n_theta + 2 * self.C:
-            th = torch.cat([th, th.new_zeros(K, self.n_theta + 2 * self.C - th.shape[1])], 1)
+        th = self._pad_params(th)
         S = K * B
         fr = self._frags(th, K)
         part = self._buf("part", S * self.tiles_last * self.C, torch.float32)
@@ -572,12 +558,7 @@ class HeaMfmaProgram:
     def shift_owners(self) -> list:
         """Per forward pass j <= fwd_last: the theta indices whose rotation it applies (layer 1 is generated in
         pass 0; rotation group g of pass j carries theta_slot(layer, q) and its phase partner)."""
-        if self.amplitude:
-            raise ValueError("prefix-reuse parameter shift is angle-only: an amplitude program's shifted circuits run "
-                             "as parameter rows of expz(init=...) (VQCEngine.param_shift_batched)")
-        if self.ring:
-            raise ValueError("prefix-reuse parameter shift is chain-only: a ring program's shifted circuits run as "
-                             "parameter rows of expz (VQCEngine.param_shift_batched)")
+        self._need_prefix_reuse()
         own = [[] for _ in range(self.fwd_last + 1)]
         for q in range(self.n):
             own[0] += [self.plan.theta_slot(1, q), self.plan.theta_slot(1, q) + 1]
@@ -628,8 +609,7 @@ class HeaMfmaProgram:
         E = ext()
         x, th, K, B = self._prep(xang, params)
         P, C, n = self.n_theta, self.C, self.n
-        if th.shape[1] < P + 2 * C:
-            th = torch.cat([th, th.new_zeros(K, P + 2 * C - th.shape[1])], 1)
+        th = self._pad_params(th)
         ps = th.shape[1]
         F = self.fwd_last + 1
         own = self.shift_owners()
@@ -703,12 +683,7 @@ class HeaMfmaProgram:
         f', so m is not needed (no +pi branches).  Work is chunked over clients and over shifted rows to fit
         ``_shift_budget`` (0.4 of free HBM).  ``exact_only``: skip the readout model (tests).
         w = dL/d<Z>_noisy [K, B, C] -> [K, n_theta]."""
-        if self.amplitude:
-            raise ValueError("prefix-reuse parameter shift is angle-only: an amplitude program's shifted circuits run "
-                             "as parameter rows of expz(init=...) (VQCEngine.param_shift_batched)")
-        if self.ring:
-            raise ValueError("prefix-reuse parameter shift is chain-only: a ring program's shifted circuits run as "
-                             "parameter rows of expz (VQCEngine.param_shift_batched)")
+        self._need_prefix_reuse()
         K, B, C = w.shape
         P = self.n_theta
         noisy = noise is not None and not exact_only

@@ -29,8 +29,11 @@ GEMMs (MFMA, ``csrc/hea_mfma.hip``) instead of per-gate VALU sweeps:
 
 * **Ring entanglers.**  A ring layer is the linear map R = C P (P, then bit 0 flips when bit n-1 is set), so the
   same frames cover it (``frame_vec`` / ``frame_rows`` with ``ring=True``) and the kernels, which only see tables,
-  run ring plans unchanged.  R is not triangular: ``_ring_plan`` orders rotations by the exact commutation rule
+  run ring plans unchanged.  R is not triangular: a ring plan orders rotations by the exact commutation rule
   (``ring_rotations``) and keeps what does not commute with a not-yet-measured layer-1 rotation out of early passes.
+* **One planner loop.**  ``_plan_passes`` plans every entangler; the entangler picks its rotations and dependencies
+  (``chain_rotations`` / ``ring_rotations``) and the tile of a later pass (``_staircase_tile`` / ``_scored_tile``).
+  ``plan_pair`` chooses the forward and the adjoint plan of a program.
 
 Everything here is host-side planning (runs once per circuit shape).  ``emulate`` executes a plan
 tile by tile with exactly the kernel's addressing tables in float64 numpy: it is the oracle the CPU
@@ -219,36 +222,8 @@ class HEAPlan:
         return 2 * ((layer - 1) * self.n + q)
 
 
-def eligible(spec) -> bool:
-    """Circuits this engine covers: angle feature map, RX/RZ layers, chain (or no) entangler, no noise."""
-    return (not spec.amplitude and not spec.noisy and spec.entangler in ("chain", "none")
-            and spec.feature_map.lower() in ("rx", "ry", "rz") and spec.n_qubits >= 8
-            and spec.n_qubits <= 30 and spec.n_classes <= MAX_CLASSES)
-
-
-def eligible_amplitude(spec) -> bool:
-    """Amplitude-encoded circuits this engine covers when asked for explicitly (``state_dtype: mfma | fp16 |
-    mfma_bf16``): RX/RZ layers from layer 1 on over a staged input state (csrc/hea_amp.hip), chain (or no) entangler,
-    no gate noise.  ``eligible`` stays False for them: ``auto`` keeps amplitude inputs on the fp32 VALU engine."""
-    return (spec.amplitude and not spec.noisy and spec.entangler in ("chain", "none") and spec.n_qubits >= 8
-            and spec.n_qubits <= 30 and spec.n_classes <= MAX_CLASSES)
-
-
-def eligible_ring(spec) -> bool:
-    """Ring-entangler circuits this engine covers when asked for explicitly (``state_dtype: mfma | fp16 | mfma_bf16``):
-    angle features, RX/RZ layers, no gate noise, 8..30 qubits (so n > 2: the ring is closed), <= 8 classes.
-    ``eligible`` stays False for them: ``auto`` / ``bf16`` keep ring circuits on the VALU engine.  Amplitude-encoded
-    ring circuits stay refused (the VALU engine runs them), although the planner and the emulator handle them
-    (``build_plan(feature="amplitude", ring=True)``)."""
-    return (spec.entangler == "ring" and not spec.noisy and not spec.amplitude
-            and spec.feature_map.lower() in ("rx", "ry", "rz")
-            and 8 <= spec.n_qubits <= 30 and spec.n_classes <= MAX_CLASSES)
-
-
-def refusal(spec) -> str:
-    """Why none of ``eligible`` / ``eligible_amplitude`` / ``eligible_ring`` holds for ``spec`` ('' if one does)."""
-    if eligible(spec) or eligible_amplitude(spec) or eligible_ring(spec):
-        return ""
+def _refusals(spec) -> list:
+    """Every bound of the engine that ``spec`` breaks (none: the engine runs it, as the circuit kind ``_kind`` names)."""
     why = []
     if spec.noisy:
         why.append("gate noise (Pauli trajectories) runs on the VALU engine only")
@@ -262,7 +237,41 @@ def refusal(spec) -> str:
         why.append(f"entangler {spec.entangler!r} is not chain | ring | none")
     if not spec.amplitude and spec.feature_map.lower() not in ("rx", "ry", "rz"):
         why.append(f"feature map {spec.feature_map!r} is not rx | ry | rz | amplitude")
-    return "; ".join(why) or "unsupported circuit"
+    return why
+
+
+def _kind(spec) -> str:
+    """'angle' | 'amplitude' | 'ring' for an RX/RZ-layer circuit inside the bounds (8..30 qubits, <= 8 classes, no gate
+    noise, chain / ring / no entangler, rx | ry | rz | amplitude features), '' for every other."""
+    if _refusals(spec):
+        return ""
+    return "ring" if spec.entangler == "ring" else "amplitude" if spec.amplitude else "angle"
+
+
+def eligible(spec) -> bool:
+    """Circuits this engine covers: angle feature map, RX/RZ layers, chain (or no) entangler, no noise."""
+    return _kind(spec) == "angle"
+
+
+def eligible_amplitude(spec) -> bool:
+    """Amplitude-encoded circuits this engine covers when asked for explicitly (``state_dtype: mfma | fp16 |
+    mfma_bf16``): RX/RZ layers from layer 1 on over a staged input state (csrc/hea_amp.hip), chain (or no) entangler,
+    no gate noise.  ``eligible`` stays False for them: ``auto`` keeps amplitude inputs on the fp32 VALU engine."""
+    return _kind(spec) == "amplitude"
+
+
+def eligible_ring(spec) -> bool:
+    """Ring-entangler circuits this engine covers when asked for explicitly (``state_dtype: mfma | fp16 | mfma_bf16``):
+    angle features, RX/RZ layers, no gate noise, 8..30 qubits (so n > 2: the ring is closed), <= 8 classes.
+    ``eligible`` stays False for them: ``auto`` / ``bf16`` keep ring circuits on the VALU engine.  Amplitude-encoded
+    ring circuits stay refused (the VALU engine runs them), although the planner and the emulator handle them
+    (``build_plan(feature="amplitude", ring=True)``)."""
+    return _kind(spec) == "ring"
+
+
+def refusal(spec) -> str:
+    """Why none of ``eligible`` / ``eligible_amplitude`` / ``eligible_ring`` holds for ``spec`` ('' if one does)."""
+    return "; ".join(_refusals(spec))
 
 
 _PLAN_CACHE: dict = {}
@@ -281,8 +290,8 @@ def build_plan(n: int, L: int, readout, chain: bool = True, feature: str = "ry",
 
     ``ring=True`` (or ``chain="ring"``): a ring entangler.  Frames count ring layers (``frame_vec(..., ring=True)``),
     dependencies are the exact commutation DAG and an angle plan keeps every rotation that does not commute with a
-    not-yet-measured layer-1 rotation out of the early passes (``_ring_plan``).  Chain / no-entangler plans do not go
-    through that code."""
+    not-yet-measured layer-1 rotation out of the early passes.  One loop plans every entangler (``_plan_passes``);
+    the ring differs in its rotations (``ring_rotations``) and in how a later pass picks its tile (``_scored_tile``)."""
     if chain == "ring":
         chain, ring = False, True
     key = (n, L, tuple(readout), chain, feature, tile_bits, swizzle)
@@ -291,122 +300,31 @@ def build_plan(n: int, L: int, readout, chain: bool = True, feature: str = "ry",
         key += ("ring",)
     if trim is None and key in _PLAN_CACHE:          # the candidate search runs once per circuit shape
         return copy.deepcopy(_PLAN_CACHE[key])
-    amp = feature.lower() == "amplitude"
-    first = 1 if amp else 2                      # first layer planned as rotation groups
+    first = 1 if feature.lower() == "amplitude" else 2      # first layer planned as rotation groups
     if ring and n <= 2:
         raise ValueError("a ring entangler needs more than 2 qubits (VQCSpec closes the ring for n > 2 only)")
-    if trim is None:
-        # candidates: no trimming, trimming everywhere, and per-layer trimming of the first (product-state)
-        # pass with the later passes greedy or trimmed; ties keep the earlier candidate
-        opts = [False, True]
-        for m in range(1, 1 << max(L + 1 - first, 0)):
-            opts += [(m << first,), (m << first, -1)]
-        cands = []
-        for tr in opts:
-            try:
-                cands.append(build_plan(n, L, readout, chain, feature, tile_bits, False, tr, ring))
-            except RuntimeError:
-                continue
-        best = min(cands, key=lambda pl: (len(pl.passes), sum(len(p.groups) for p in pl.passes)))
-        if swizzle:
-            for j, p in enumerate(best.passes):
-                layout_pass(best, p, seed=j)
-        _PLAN_CACHE[key] = copy.deepcopy(best)
-        return best
-    if ring:
-        plan = _ring_plan(n, L, readout, feature, tile_bits, trim)
-        if swizzle:
-            for j, p in enumerate(plan.passes):
-                layout_pass(plan, p, seed=j)
-        return plan
-    t = min(tile_bits, n)
-    if t < GROUP + 4:
-        raise ValueError("the MFMA engine needs at least 8 tile qubits (16 columns per MFMA block)")
-    frame = (lambda layer: layer - 1) if chain else (lambda layer: 0)
-    sup = {}
-    for layer in range(first, L + 1):
-        for q in range(n):
-            sup[(layer, q)] = frame_vec(q, frame(layer), n)
-    preds = {}
-    for (layer, q), s in sup.items():
-        preds[(layer, q)] = [(layer - 1, p) for p in range(n) if layer > first and (sup[(layer - 1, p)] & s)]
-    remaining = sorted(sup, key=lambda o: (o[0], o[1]))
-    done = set()
-    passes = []
-    while True:
-        if not passes:
-            p = Pass(t, t, t) if n > t else Pass(n, n, n)
-        else:
-            mc = min(MIN_CONTIG, max(2, t - 6))
-            low = lambda o: min(b for b in range(n) if (sup[o] >> b) & 1)
-            lo_all = min(low(o) for o in remaining)      # one pass for everything left, if it fits
-            ready = [o for o in remaining if all(d in done for d in preds[o])]
-            lo_min = lo_all if t - (n - lo_all) >= mc else min(low(o) for o in ready)
-            w = n - lo_min
-            if t - w >= mc:
-                p = Pass(t - w, lo_min, n)
-            else:
-                base = max(lo_min, mc)
-                p = Pass(mc, base, min(n, base + t - mc))
-        tm = p.mask()
-        taken = []
-        for o in remaining:
-            if (sup[o] & ~tm) == 0 and all(d in done or d in taken for d in preds[o]):
-                taken.append(o)
-        if isinstance(trim, tuple):         # per-pass layer masks (bit l = trim layer l; -1 = all layers)
-            j = len(passes)
-            layers = trim[j] if j < len(trim) else (-1 if trim[-1] == -1 else 0)
-        else:
-            layers = -1 if trim else 0
-        if layers and len(taken) < len(remaining):
-            taken = _trim_ragged(taken, preds, layers)
-        if not taken and remaining:
-            raise RuntimeError(f"pass planner stuck at {len(passes)} passes (n={n}, L={L}, t={t})")
-        for o in taken:
-            done.add(o)
-        remaining = [o for o in remaining if o not in done]
-        by_layer = {}
-        for (layer, q) in taken:
-            by_layer.setdefault(layer, []).append(q)
-        for layer in sorted(by_layer):
-            qs = sorted(by_layer[layer])
-            for i in range(0, len(qs), GROUP):
-                p.groups.append(Group(layer, qs[i:i + GROUP], frame(layer)))
-        passes.append(p)
-        if not remaining:
-            break
-        if len(passes) > 16:
-            raise RuntimeError("pass planner did not converge")
-    # every qubit's bit must sit in some tile (layer-1 gradients): add group-free passes for the rest
-    covered = (1 << n) - 1 if amp else 0        # (amplitude plans: layer 1 is in the rotation groups)
-    for p in passes:
-        covered |= p.mask()
-    while covered != (1 << n) - 1:
-        top = (1 << n) - 1 & ~covered
-        lo = max(top.bit_length() - (t - MIN_CONTIG), min(b for b in range(n) if (top >> b) & 1))
-        lo = max(lo, MIN_CONTIG)
-        p = Pass(t - (min(n, lo + t - MIN_CONTIG) - lo), lo, min(n, lo + t - MIN_CONTIG))
-        passes.append(p)
-        covered |= p.mask()
-    # layer-1 gradient groups: first pass whose tile holds the qubit's bit (none in an amplitude plan)
-    owner = {}
-    for q in range(0 if amp else n):
-        for j, p in enumerate(passes):
-            if (p.mask() >> q) & 1:
-                owner[q] = j
-                break
-    for j, p in enumerate(passes):
-        qs = [q for q in owner if owner[q] == j]
-        for i in range(0, len(qs), GROUP):
-            p.l1.append(Group(1, qs[i:i + GROUP], 0))
-    slot = 0
-    for p in passes:
-        for g in p.groups:
-            g.slot = slot
-            slot += 1
-    plan = HEAPlan(n, L, len(readout), list(readout), chain, feature, t, passes, slot)
+    if trim is not None:
+        return _layout(_plan_passes(n, L, readout, chain, ring, feature, tile_bits, trim), swizzle)
+    # candidates: no trimming, trimming everywhere, and per-layer trimming of the first (product-state)
+    # pass with the later passes greedy or trimmed; ties keep the earlier candidate
+    opts = [False, True]
+    for m in range(1, 1 << max(L + 1 - first, 0)):
+        opts += [(m << first,), (m << first, -1)]
+    cands = []
+    for tr in opts:
+        try:
+            cands.append(_plan_passes(n, L, readout, chain, ring, feature, tile_bits, tr))
+        except RuntimeError:
+            continue
+    best = _layout(min(cands, key=lambda pl: (len(pl.passes), sum(len(p.groups) for p in pl.passes))), swizzle)
+    _PLAN_CACHE[key] = copy.deepcopy(best)
+    return best
+
+
+def _layout(plan: HEAPlan, swizzle: bool = True) -> HEAPlan:
+    """``plan`` with every pass' LDS layout searched (``layout_pass``; ``swizzle=False``: left at the identity)."""
     if swizzle:
-        for j, p in enumerate(passes):
+        for j, p in enumerate(plan.passes):
             layout_pass(plan, p, seed=j)
     return plan
 
@@ -450,6 +368,17 @@ def _assign_l1(passes: list, n: int, amp: bool) -> None:
         p.l1 = [Group(1, qs[i:i + GROUP], 0) for i in range(0, len(qs), GROUP)]
 
 
+def chain_rotations(n: int, L: int, first: int, chain: bool = True) -> tuple:
+    """The ``ring_rotations`` of a chain (``chain=False``: no entangler) circuit: per rotation (layer, q) its memory
+    vector u = P^-(l-1) e_q (e_q without entangler), and ``preds``, the rotations of the layer directly below whose
+    vectors overlap it.  P is triangular, so that covers every dependency and a rotation never has to wait for a
+    layer-1 gradient to be measured: no row masks (0)."""
+    u = {(layer, q): frame_vec(q, layer - 1 if chain else 0, n) for layer in range(first, L + 1) for q in range(n)}
+    preds = {(layer, q): [(layer - 1, p) for p in range(n) if layer > first and (u[(layer - 1, p)] & s)]
+             for (layer, q), s in u.items()}
+    return u, dict.fromkeys(u, 0), preds
+
+
 def ring_rotations(n: int, L: int, first: int) -> tuple:
     """Per rotation (layer, q) of a ring circuit its memory vector u = R^-(l-1) e_q and row mask r = row q of R^(l-1),
     and ``preds``: every rotation of an earlier layer it does not commute with.  Rotations a, b of different layers
@@ -466,75 +395,94 @@ def ring_rotations(n: int, L: int, first: int) -> tuple:
     return u, r, preds
 
 
-def _ring_plan(n: int, L: int, readout, feature: str, tile_bits: int, trim) -> HEAPlan:
-    """One ring plan (no swizzle) for a trim option of ``build_plan``.  Pass 0 is the low t bits (it generates the
-    product state or loads the staged input); every later pass takes the tile (c low bits from the minimum contiguous
-    run up to t, a window anywhere above) that admits the most rotations, ties broken by newly covered bits.  A
-    rotation joins a pass when its vector lies in the tile, every non-commuting rotation of an earlier layer is done
-    (``ring_rotations``: the exact DAG) and - angle plans - it commutes with the layer-1 rotation (u = r = e_q) of every
-    qubit q no tile has covered yet: q's 2 x 2 cross matrix is measured at the input of the first pass whose tile
-    holds bit q, which is only the layer-1 gradient if everything run before commutes with it."""
+def _staircase_tile(n: int, t: int, mc: int, u: dict, preds: dict, remaining: list, done: set) -> Pass:
+    """A later pass of a chain plan: the top window reaching down to the lowest bit of what is left if that keeps
+    ``mc`` contiguous low bits (one pass for everything left), else down to the lowest bit of what is ready."""
+    low = lambda o: min(b for b in range(n) if (u[o] >> b) & 1)
+    lo_all = min(low(o) for o in remaining)
+    ready = [o for o in remaining if all(d in done for d in preds[o])]
+    lo_min = lo_all if t - (n - lo_all) >= mc else min(low(o) for o in ready)
+    w = n - lo_min
+    if t - w >= mc:
+        return Pass(t - w, lo_min, n)
+    base = max(lo_min, mc)
+    return Pass(mc, base, min(n, base + t - mc))
+
+
+def _scored_tile(n: int, t: int, mc: int, admit, covered: int) -> Pass:
+    """A later pass of a ring plan: the tile (c low bits from ``mc`` up to t, a window anywhere above) that admits the
+    most rotations, ties broken by newly covered bits, then by the longer contiguous run."""
+    best = None
+    for c in range(t, mc - 1, -1):
+        w = t - c
+        for lo in ([c] if w == 0 else range(c + 1, n - w + 1)):
+            cand = Pass(c, lo, lo + w)
+            score = (len(admit(cand)), bin(cand.mask() & ~covered).count("1"))
+            if best is None or score > best[0]:
+                best = (score, cand)
+    return best[1]
+
+
+def _plan_passes(n: int, L: int, readout, chain: bool, ring: bool, feature: str, tile_bits: int, trim) -> HEAPlan:
+    """One plan (no swizzle) for a trim option of ``build_plan``.  Pass 0 is the low t bits (it generates the product
+    state or loads the staged input); a later pass takes the tile its entangler's rule picks (``_staircase_tile`` /
+    ``_scored_tile``).  A rotation joins a pass when its vector lies in the tile, every rotation it depends on is done
+    or joined earlier in the pass (``chain_rotations`` / ``ring_rotations``) and - ring angle plans - it commutes with
+    the layer-1 rotation (u = r = e_q) of every qubit q no tile has covered yet: q's 2 x 2 cross matrix is measured at
+    the input of the first pass whose tile holds bit q, which is only the layer-1 gradient if everything run before
+    commutes with it."""
     amp = feature.lower() == "amplitude"
     first = 1 if amp else 2
     t = min(tile_bits, n)
     if t < GROUP + 4:
         raise ValueError("the MFMA engine needs at least 8 tile qubits (16 columns per MFMA block)")
+    mc = min(MIN_CONTIG, max(2, t - 6))
     full = (1 << n) - 1
-    u, r, preds = ring_rotations(n, L, first)
+    u, r, preds = ring_rotations(n, L, first) if ring else chain_rotations(n, L, first, chain)
+    name = "ring pass planner" if ring else "pass planner"
     remaining = sorted(u)
     done = set()
     passes = []
-    covered = full if amp else 0
+    covered = full if amp else 0                # (amplitude plans: layer 1 is in the rotation groups)
 
     def admit(p):
         tm = p.mask()
-        open_bits = full & ~(covered | tm)           # layer-1 qubits measured in a later pass
+        open_bits = full & ~(covered | tm)      # layer-1 qubits measured in a later pass
         taken, have = [], set(done)
         for o in remaining:
-            ok = (u[o] & ~tm) == 0 and not ((u[o] | r[o]) & open_bits)
-            if ok and all(d in have for d in preds[o]):
+            if (u[o] & ~tm) == 0 and not (r[o] & open_bits) and all(d in have for d in preds[o]):
                 taken.append(o)
                 have.add(o)
         return taken
 
-    while remaining:
+    # a chain plan with nothing to place (L = 1 angle) still gets pass 0; such a ring plan is its coverage passes only
+    while remaining or not (ring or passes):
         if not passes:
             p = Pass(t, t, t)
-            taken = admit(p)
+        elif ring:
+            p = _scored_tile(n, t, mc, admit, covered)
         else:
-            mc = min(MIN_CONTIG, max(2, t - 6))
-            best = None
-            for c in range(t, mc - 1, -1):          # (ties keep the longer contiguous run)
-                w = t - c
-                for lo in ([c] if w == 0 else range(c + 1, n - w + 1)):
-                    cand = Pass(c, lo, lo + w)
-                    tk = admit(cand)
-                    score = (len(tk), bin(cand.mask() & ~covered).count("1"))
-                    if best is None or score > best[0]:
-                        best = (score, cand, tk)
-            score, p, taken = best
-            if score == (0, 0):
-                raise RuntimeError(f"ring pass planner stuck at {len(passes)} passes (n={n}, L={L}, t={t})")
+            p = _staircase_tile(n, t, mc, u, preds, remaining, done)
+        taken = admit(p)
+        if remaining and not taken and not (ring and p.mask() & ~covered):    # (a ring pass may only cover new bits)
+            raise RuntimeError(f"{name} stuck at {len(passes)} passes (n={n}, L={L}, t={t})")
         if isinstance(trim, tuple):         # per-pass layer masks (bit l = trim layer l; -1 = all layers)
             j = len(passes)
             layers = trim[j] if j < len(trim) else (-1 if trim[-1] == -1 else 0)
         else:
             layers = -1 if trim else 0
-        if layers and taken and len(taken) < len(remaining):
+        if layers and len(taken) < len(remaining):
             taken = _trim_ragged(taken, preds, layers)
         done.update(taken)
         remaining = [o for o in remaining if o not in done]
-        by_layer = {}
-        for (layer, q) in taken:
-            by_layer.setdefault(layer, []).append(q)
-        for layer in sorted(by_layer):
-            qs = sorted(by_layer[layer])
+        for layer in sorted({o[0] for o in taken}):
+            qs = sorted(q for (l, q) in taken if l == layer)
             for i in range(0, len(qs), GROUP):
-                p.groups.append(Group(layer, qs[i:i + GROUP], layer - 1, ring=True))
+                p.groups.append(Group(layer, qs[i:i + GROUP], layer - 1 if chain or ring else 0, ring=ring))
         covered |= p.mask()
         passes.append(p)
-        if len(passes) > 16:
-            raise RuntimeError("ring pass planner did not converge")
+        if len(passes) > 16 and (ring or remaining):
+            raise RuntimeError(f"{name} did not converge")
     while covered != full:                  # (angle plans) group-free passes for bits no tile holds yet
         top = full & ~covered
         lo = max(top.bit_length() - (t - MIN_CONTIG), min(b for b in range(n) if (top >> b) & 1))
@@ -543,19 +491,17 @@ def _ring_plan(n: int, L: int, readout, feature: str, tile_bits: int, trim) -> H
         passes.append(p)
         covered |= p.mask()
     _assign_l1(passes, n, amp)
-    slot = 0
-    for p in passes:
-        for g in p.groups:
-            g.slot = slot
-            slot += 1
-    return HEAPlan(n, L, len(readout), list(readout), False, feature, t, passes, slot, ring=True)
+    groups = [g for p in passes for g in p.groups]
+    for slot, g in enumerate(groups):
+        g.slot = slot
+    return HEAPlan(n, L, len(readout), list(readout), chain, feature, t, passes, len(groups), ring=ring)
 
 
 def widen_plan(plan: HEAPlan, tile_bits: int, swizzle: bool = True) -> HEAPlan:
     """The plan with the same rotation groups (and slots) per pass as ``plan`` on tiles of ``tile_bits`` bits: every
     pass tile is widened (low run first, then the window downwards, then upwards), so each group's support stays
     inside it.  Layer-1 gradient groups are reassigned to the first tile holding their bit: tiles only grow, so every
-    bit is covered no later than before and the layer-1 commutation rule keeps holding.  ``HeaMfmaProgram`` runs a ring
+    bit is covered no later than before and the layer-1 commutation rule keeps holding.  ``plan_pair`` runs a ring
     forward on this (2^14 tiles) over a 2^13 adjoint plan: the two then have the same passes by construction."""
     n = plan.n
     t = min(tile_bits, n)
@@ -583,13 +529,42 @@ def widen_plan(plan: HEAPlan, tile_bits: int, swizzle: bool = True) -> HEAPlan:
             raise RuntimeError("a widened tile lost bits")
         passes.append(q)
     _assign_l1(passes, n, plan.amplitude)
-    out = HEAPlan(n, plan.L, plan.C, list(plan.readout), plan.chain, plan.feature, t, passes, plan.n_slots,
-                  ring=plan.ring)
-    if swizzle:
-        for j, p in enumerate(passes):
-            layout_pass(out, p, seed=j)
+    out = _layout(HEAPlan(n, plan.L, plan.C, list(plan.readout), plan.chain, plan.feature, t, passes, plan.n_slots,
+                          ring=plan.ring), swizzle)
     _PLAN_CACHE[key] = copy.deepcopy(out)
     return out
+
+
+def same_passes(a: HEAPlan, b: HEAPlan) -> bool:
+    """Two plans run the same rotation groups (and unitary slots) in the same passes - only their tile geometry
+    differs.  The layer-1 gradient groups may sit in other passes: they exist only in the adjoint programs
+    (the forward generates the whole layer-1 product state in its first pass)."""
+    def sig(plan):
+        return [sorted((g.slot, g.layer, tuple(g.qubits), g.frame) for g in p.groups) for p in plan.passes]
+    return a.n_slots == b.n_slots and sig(a) == sig(b)
+
+
+def plan_pair(n: int, L: int, readout, entangler: str, feature: str, tile_bits: int, adj_tile_bits: int,
+              ring_fwd_from_adj: bool = True) -> tuple:
+    """(forward plan, adjoint plan) of a program.  The adjoint may run on smaller tiles than the forward (2^13
+    amplitudes: two adjoint workgroups per CU, one's tile load hidden behind the other's group ops) when that plan has
+    the same passes, rotation groups and unitary slots: pass outputs are stored in memory order, so the tiling of a
+    pass is free to differ.  A ring's independently planned small-tile plan groups its rotations differently:
+    ``ring_fwd_from_adj`` runs the forward on that plan's groups, each pass tile widened to the forward size
+    (``widen_plan``).  Otherwise the forward plan serves as both."""
+    ring = entangler == "ring"
+    fwd = build_plan(n, L, readout, entangler == "chain", feature, tile_bits, ring=ring)
+    if adj_tile_bits == tile_bits:
+        return fwd, fwd
+    adj = build_plan(n, L, readout, entangler == "chain", feature, adj_tile_bits, ring=ring)
+    if same_passes(fwd, adj):
+        return fwd, adj
+    if ring and ring_fwd_from_adj and adj_tile_bits < tile_bits and len(adj.passes) <= len(fwd.passes):
+        fwd = widen_plan(adj, tile_bits)
+        if not same_passes(fwd, adj):
+            raise RuntimeError("the widened ring plan lost a group of its source plan")
+        return fwd, adj
+    return fwd, fwd
 
 
 # ---------------------------------------------------------------------------------------- op tables
