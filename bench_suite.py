@@ -71,6 +71,12 @@ SUITE = {
                            "privacy.noise_mode=distributed", "privacy.secure_agg=true", "train.weighting=uniform"],
                           "client local-steps/sec (20-qubit VQC x 64 non-IID clients, distributed DP + SecAgg, "
                           "fp16 MFMA engine)", None),
+    # record-level DP-SGD at the headline shape: Poisson lots, per-sample clipping and lot noise from the MFMA engine's
+    # gradient slab (csrc/hea_dpsgd.hip); epsilon in the line is per record
+    "vqc16q_dpsgd64_mfma": ("configs/headline_16q_dpsgd.yaml",
+                            ["model.state_dtype=mfma", "privacy.deterministic_noise=true"],
+                            "client local-steps/sec (16-qubit VQC x 64 clients, record-level DP-SGD, fp16 MFMA engine)",
+                            None),
     "vqc48q_mps64": ("configs/mps_48q_64clients.yaml", [],
                      "client local-steps/sec (48-qubit VQC x 64 clients, MPS tensor-network backend)", None),
     # amplitude-encoded 28 x 28 digits in 10 qubits: the MFMA engine (staged fp16 input states) against the fp32 VALU
@@ -175,7 +181,7 @@ def main():
                        "shots": cfg.noise.shots},
         }
         if cfg.privacy.dp:
-            rec["dp"] = {"noise_mode": cfg.privacy.noise_mode, "noise_multiplier": cfg.privacy.noise_multiplier,
+            rec["dp"] = {"level": cfg.privacy.level, "noise_mode": cfg.privacy.noise_mode, "noise_multiplier": cfg.privacy.noise_multiplier,
                          "clip_norm": cfg.privacy.clip_norm, "delta": cfg.privacy.delta,
                          # accounted rounds = the sum of the history's step counts (the accountant merges equal
                          # (q, sigma) rounds into one record); q next to epsilon.  Every round that ran is charged:

@@ -87,6 +87,11 @@ class TrainConfig:
 @dataclass
 class PrivacyConfig:
     dp: bool = False
+    # client: the aggregator clips each client's whole update and noises it; epsilon is per client (the default).
+    # record: DP-SGD inside the local steps - every example's gradient clipped to C, N(0, sigma^2 C^2) added to each
+    # Poisson lot's sum; epsilon is per record and the aggregator adds nothing (VQC, adjoint gradients, MFMA engine
+    # or torch backend; docs/ARCHITECTURE.md "Record-level DP-SGD")
+    level: str = "client"
     clip_norm: float = 1.0              # C (ROADMAP:50)
     noise_multiplier: float = 1.0       # sigma (ROADMAP:51)
     delta: float = 1e-5

@@ -24,6 +24,14 @@ int qfx_hea_grad_reduce(const long long* gslab, int slab_tiles, int n_gradops, c
 int qfx_hea_readout_rec(const float* part, int tps, int C, int spc, int K, const long long* y, const float* wts,
                         const float* params, int p_stride, int n_theta, float* expz, float* wread, float* rec,
                         hipStream_t st);
+// record-level DP-SGD reductions (hea_dpsgd.hip)
+int qfx_hea_dp_norm(const long long* gslab, int slab_tiles, int n_gradops, const int* gmeta, int spc, int K,
+                    const float* params, int p_stride, const float* rec, int C, int n_theta, double clip, double* norm,
+                    double* cfac, hipStream_t st);
+int qfx_hea_dp_reduce(const long long* gslab, int slab_tiles, int n_gradops, const int* gmeta, int spc, int K,
+                      const float* params, int p_stride, const float* rec, const float* wts, const double* cfac, int C,
+                      int n_theta, const long long* keys, long long step, double sigma, double clip, double lot,
+                      float* grad, float* loss, float* correct, hipStream_t st);
 int qfx_hea_args_size();
 int qfx_hea_check_status(hipStream_t st);
 // bf16 state storage (hea_mfma_bf16.hip)
@@ -327,6 +335,53 @@ void hea_grad_reduce(torch::Tensor gslab, int64_t slab_tiles, int64_t n_gradops,
         "qfx_hea_grad_reduce");
 }
 
+// Record-level DP-SGD (hea_dpsgd.hip), in place of hea_grad_reduce on a step's slab and readout records
+// (rec [K * spc, 2C + 2]).  hea_dp_norm: every sample's gradient norm and clip factor (float64 [K * spc]).
+void dp_shapes(const char* who, int64_t slab_tiles, int64_t n_gradops, int64_t spc, int64_t K, const torch::Tensor& params,
+               int64_t C, int64_t n_theta) {
+  need(C >= 1 && C <= 8 && spc >= 1 && K >= 0 && slab_tiles >= 1 && n_gradops >= 0,
+       std::string(who) + ": 1..8 classes, >= 1 sample per client and slab tile");
+  need(params.dim() == 2 && params.size(0) >= K, std::string(who) + ": params must be [K, p_stride]");
+  need(n_theta >= 0 && n_theta + 2 * C <= params.size(1), std::string(who) + ": readout parameters past the parameter row");
+  need(K * spc <= 0x7fffffffLL, std::string(who) + ": too many samples for one launch");
+}
+
+void hea_dp_norm(torch::Tensor gslab, int64_t slab_tiles, int64_t n_gradops, torch::Tensor gmeta, int64_t spc, int64_t K,
+                 torch::Tensor params, torch::Tensor rec, int64_t C, int64_t n_theta, double clip, torch::Tensor norm,
+                 torch::Tensor cfac) {
+  dp_shapes("dp_norm", slab_tiles, n_gradops, spc, K, params, C, n_theta);
+  need(clip > 0.0, "dp_norm: the clip norm must be positive");
+  const int64_t S = K * spc, p_stride = params.size(1);
+  check(qfx_hea_dp_norm(dp<long long>(gslab, torch::kInt64, "gslab", S * slab_tiles * n_gradops * 32), (int)slab_tiles,
+                        (int)n_gradops, dp<int>(gmeta, torch::kInt32, "gmeta", n_gradops * 10), (int)spc, (int)K,
+                        dp<float>(params, torch::kFloat32, "params", K * p_stride), (int)p_stride,
+                        dp<float>(rec, torch::kFloat32, "rec", S * (2 * C + 2)), (int)C, (int)n_theta, clip,
+                        dp<double>(norm, torch::kFloat64, "norm", S), dp<double>(cfac, torch::kFloat64, "cfac", S), cur()),
+        "qfx_hea_dp_norm");
+}
+
+// hea_dp_reduce: grad [K, p_stride] entries 0 .. n_theta + 2C - 1 = (sum_s cfac_s g_s + sigma clip z) / lot with z the
+// Philox normals of elements step P + i of the client's key (keys int64 [K, 2], a device table; unused with sigma = 0),
+// and the clients' loss / hits [K] over the live samples (wts > 0).
+void hea_dp_reduce(torch::Tensor gslab, int64_t slab_tiles, int64_t n_gradops, torch::Tensor gmeta, int64_t spc,
+                   int64_t K, torch::Tensor params, torch::Tensor rec, torch::Tensor wts, torch::Tensor cfac, int64_t C,
+                   int64_t n_theta, torch::Tensor keys, int64_t step, double sigma, double clip, double lot,
+                   torch::Tensor grad, torch::Tensor loss, torch::Tensor correct) {
+  dp_shapes("dp_reduce", slab_tiles, n_gradops, spc, K, params, C, n_theta);
+  need(clip > 0.0 && sigma >= 0.0 && lot > 0.0 && step >= 0, "dp_reduce: clip > 0, sigma >= 0, lot > 0, step >= 0");
+  const int64_t S = K * spc, p_stride = params.size(1);
+  check(qfx_hea_dp_reduce(dp<long long>(gslab, torch::kInt64, "gslab", S * slab_tiles * n_gradops * 32), (int)slab_tiles,
+                          (int)n_gradops, dp<int>(gmeta, torch::kInt32, "gmeta", n_gradops * 10), (int)spc, (int)K,
+                          dp<float>(params, torch::kFloat32, "params", K * p_stride), (int)p_stride,
+                          dp<float>(rec, torch::kFloat32, "rec", S * (2 * C + 2)), dp<float>(wts, torch::kFloat32, "wts", S),
+                          dp<double>(cfac, torch::kFloat64, "cfac", S), (int)C, (int)n_theta,
+                          dp<long long>(keys, torch::kInt64, "keys", sigma > 0.0 ? 2 * K : 0), (long long)step, sigma,
+                          clip, lot, dp<float>(grad, torch::kFloat32, "grad", K * p_stride),
+                          dp<float>(loss, torch::kFloat32, "loss", K), dp<float>(correct, torch::kFloat32, "correct", K),
+                          cur()),
+        "qfx_hea_dp_reduce");
+}
+
 // Per-plan pass kernels (hea_spec.cpp).  cfg = [n, t, c, lo, hi, C, gen, load_lam, store_lam, n_regions, H0..H4,
 // bf16, stamps, gate_lo (-1: default)[, obs_load (absent: 0)]]; ops / fidx: the pass program's host tensors.
 qfx::HeaSpecDesc spec_desc(bool adjoint, torch::Tensor ops, torch::Tensor fidx, std::vector<int64_t> cfg) {
@@ -391,6 +446,14 @@ void register_hea(pybind11::module& m) {
         pybind11::arg("adam") = pybind11::none(), pybind11::arg("hyper") = pybind11::none(),
         pybind11::arg("readout") = pybind11::none(), pybind11::arg("ro_c") = 0, pybind11::arg("ro_ntheta") = 0,
         pybind11::arg("fed") = pybind11::none(), pybind11::arg("fed_wrap") = false, pybind11::arg("fed_n_norms") = 0);
+  m.def("hea_dp_norm", &hea_dp_norm, pybind11::arg("gslab"), pybind11::arg("slab_tiles"), pybind11::arg("n_gradops"),
+        pybind11::arg("gmeta"), pybind11::arg("spc"), pybind11::arg("K"), pybind11::arg("params"), pybind11::arg("rec"),
+        pybind11::arg("C"), pybind11::arg("n_theta"), pybind11::arg("clip"), pybind11::arg("norm"), pybind11::arg("cfac"));
+  m.def("hea_dp_reduce", &hea_dp_reduce, pybind11::arg("gslab"), pybind11::arg("slab_tiles"), pybind11::arg("n_gradops"),
+        pybind11::arg("gmeta"), pybind11::arg("spc"), pybind11::arg("K"), pybind11::arg("params"), pybind11::arg("rec"),
+        pybind11::arg("wts"), pybind11::arg("cfac"), pybind11::arg("C"), pybind11::arg("n_theta"), pybind11::arg("keys"),
+        pybind11::arg("step"), pybind11::arg("sigma"), pybind11::arg("clip"), pybind11::arg("lot"), pybind11::arg("grad"),
+        pybind11::arg("loss"), pybind11::arg("correct"));
   m.def("hea_args_size", []() { return qfx_hea_args_size(); });
   m.attr("HEA_STAMP_ROWS") = HEA_STAMP_ROWS;
   // -1: release build (no device checks); 0: no failure since the last read; else the failing source line

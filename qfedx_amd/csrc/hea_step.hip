@@ -3,6 +3,7 @@
 // sums and the optional fused Adam step).  hea_mfma_bf16.hip includes this file for the bf16 fragment build.
 #include "hea_common.h"
 #include "hea_frag.h"
+#include "hea_gradop.h"
 #include "qfx_fedavg.h"
 
 namespace HEA_NS {
@@ -106,22 +107,9 @@ __global__ void __launch_bounds__(256) hea_grad_reduce_kernel(const long long* _
     }
     __syncthreads();
     if (tid < nreal) {
-      const double* p = pt + 8 * tid;
-      const float* prm = params + (size_t)k * p_stride;
-      float gth, gph;
-      if (inside) {
-        // at the op input: d/dtheta = Im<lam|X|psi> = Im(n01 + n10);
-        // d/dphi = Im<lam|RX^H Z RX|psi> = cos(theta) Im(n00 - n11) + sin(theta) Re(n01 - n10)
-        const double th = prm[m[2 + tid]];
-        const double ct = cos(th), st = sin(th);
-        gth = (float)(p[3] + p[5]);
-        gph = (float)(ct * (p[1] - p[7]) + st * (p[2] - p[4]));
-      } else {
-        const double ph = prm[m[6 + tid]];
-        const double cp = cos(ph), sp = sin(ph);
-        gth = (float)((cp * p[5] - sp * p[4]) + (cp * p[3] + sp * p[2]));
-        gph = (float)(p[1] - p[7]);
-      }
+      double dth, dph;                                  // both branches (inside or not): hea_gradop.h
+      qfx::hea_gradop_pair(pt, params + (size_t)k * p_stride, m, tid, inside, dth, dph);
+      const float gth = (float)dth, gph = (float)dph;
       grad[(size_t)k * p_stride + m[2 + tid]] = gth;
       grad[(size_t)k * p_stride + m[6 + tid]] = gph;
       if (ad.m) {

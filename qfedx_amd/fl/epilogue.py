@@ -26,6 +26,7 @@ class DeviceRoundEpilogue:
     def __init__(self, runner):
         p, dev = runner.cfg.privacy, runner.device
         self.p, self.agg, self.world, self.secagg = p, runner.aggregator, runner.world, runner.secagg
+        self.client_dp = bool(getattr(runner, "client_dp", p.dp))
         self.uniform = runner.cfg.train.weighting == "uniform"
         self.noise_seed, self.num_clients = runner.noise_seed, runner.num_clients
         self.P, self.NN = runner.P, runner.n_norm_slots
@@ -47,7 +48,7 @@ class DeviceRoundEpilogue:
         """Set round r's host values and return its ``extra`` per-client tables."""
         self.r, self.ids, self.params = r, ids, params
         p, extra = self.p, {}
-        if p.dp and ids:
+        if self.client_dp and ids:      # (record-level DP noises inside the local steps: the reduce adds nothing)
             from ..ops.fedavg_hip import dp_noise_keys
             extra["dpkeys"] = dp_noise_keys(ids, r, self.noise_seed)
         if self.uniform:

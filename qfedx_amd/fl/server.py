@@ -101,6 +101,14 @@ class FederatedRunner:
             raise ValueError(f"train.sampling must be auto | fixed | poisson, got {t.sampling!r}")
         self.poisson = sampling == "poisson"
         noise_scale(getattr(p, "noise_mode", "local"), 1)           # validates privacy.noise_mode
+        level = getattr(p, "level", "client")
+        if level not in ("client", "record"):
+            raise ValueError(f"privacy.level must be client | record, got {level!r}")
+        # record-level DP (DP-SGD inside the local steps): the aggregator then neither clips nor noises
+        self.record_dp = bool(p.dp) and level == "record"
+        self.client_dp = bool(p.dp) and not self.record_dp
+        if self.record_dp:
+            self._setup_record_dp()
         if p.dp and getattr(p, "noise_mode", "local") == "distributed" and not p.secure_agg:
             # each client's share of the noise is too small to protect its update on its own: only the SecAgg sum
             # (which the server sees instead of the shares) carries the accounted sigma C
@@ -119,7 +127,7 @@ class FederatedRunner:
                                            getattr(p, "secagg_min_live", 0))
             self.secagg.setup(self.local_ids, world)
         self.aggregator = Aggregator(self.P, adapter.angle_mask(), device, backend, t.aggregate,
-                                     t.wrap_angles, p.dp, p.clip_norm, p.noise_multiplier, p.secure_agg,
+                                     t.wrap_angles, self.client_dp, p.clip_norm, p.noise_multiplier, p.secure_agg,
                                      self.secagg, self.noise_seed, num_clients=self.num_clients)
         self.accountant = RDPAccountant()
         # test shard for this rank
@@ -144,7 +152,8 @@ class FederatedRunner:
         # CC6: per-client update norms in the round all-reduce.  Opt-in NON-PRIVATE diagnostic: the raw pre-clip norms
         # (and the clip fraction / quantiles logged from them) are computed from private data without noise and are
         # not charged to the accountant, so a run that logs them is outside the epsilon it reports
-        self.n_norm_slots = self.num_clients if (p.dp and not p.secure_agg and cfg.runtime.log_client_norms) else 0
+        self.n_norm_slots = self.num_clients if (self.client_dp and not p.secure_agg
+                                                 and cfg.runtime.log_client_norms) else 0
         # CC2: the round's collective captured into the round hipGraph - decided ONCE, agreed by every rank (each
         # rank captures and replays one all-reduce, compared bitwise with an eager one; fl/trainer.py keeps a per-shape
         # eager fallback that preserves the collective order)
@@ -159,6 +168,58 @@ class FederatedRunner:
         self._counts_dev = self.store.counts.to(torch.float64).to(device)
         # the device round epilogue (HIP, no server optimizer): FedAvg reduce, collective and apply on the device
         self.epilogue = DeviceRoundEpilogue(self) if backend == "hip" and self.server_opt is None else None
+
+    # ------------------------------------------------------------------ record-level DP
+    def _setup_record_dp(self) -> None:
+        """``privacy.dp`` with ``privacy.level: record``: refuse what the mechanism does not cover (naming the config
+        key), agree on the sampling rate and the lot width, and hand the trainer its DP-SGD settings."""
+        import torch.distributed as tdist
+        cfg, t, p = self.cfg, self.cfg.train, self.cfg.privacy
+        what = "privacy.level=record"
+        if getattr(p, "noise_mode", "local") == "distributed":
+            raise ValueError(f"{what} adds its noise inside every local step: privacy.noise_mode=distributed (shares "
+                             "of a client-level noise) does not apply, use privacy.noise_mode=local")
+        if cfg.model.kind != "vqc":
+            raise ValueError(f"{what} needs per-sample gradients: model.kind=vqc only, got {cfg.model.kind!r}")
+        method = "spsa" if t.optimizer == "spsa" else t.grad_method
+        if method != "adjoint" and not (method == "autograd" and self.backend == "torch"):
+            raise ValueError(f"{what} needs train.grad_method=adjoint (autograd on the torch backend), got {method!r}: "
+                             "param_shift and spsa form no per-sample gradients")
+        if getattr(self.adapter, "noise", None) is not None:
+            raise ValueError(f"{what} needs a noiseless simulator: noise.kind={cfg.noise.kind!r} (gate / readout "
+                             "noise, shots) is not covered")
+        if getattr(self.adapter, "simulator", "statevector") != "statevector":
+            raise ValueError(f"{what} runs on model.simulator=statevector, got {self.adapter.simulator!r}")
+        eng = self.adapter.engine
+        if eng.backend == "hip" and not hasattr(eng.hip, "_dpsgd_step"):
+            raise ValueError(f"{what} on the HIP backend runs on the MFMA statevector engine: set model.state_dtype="
+                             "mfma | fp16 | mfma_bf16 for a circuit it covers (>= 8 qubits), or runtime.backend=torch")
+        if not (p.clip_norm > 0 and p.noise_multiplier >= 0):
+            raise ValueError(f"{what} needs privacy.clip_norm > 0 and privacy.noise_multiplier >= 0")
+        # q_max = max_k min(1, B / n_k) and the largest shard (the lot tables' width), identical on every rank: shard
+        # sizes are only known where the shards live, so ONE MAX all-reduce of (n_max, -n_min)
+        n = self.store.counts[self.store.counts > 0].double()
+        ext = torch.tensor([float(n.max()) if n.numel() else 0.0, -float(n.min()) if n.numel() else -float("inf")],
+                           dtype=torch.float64, device=self.world.device)
+        if self.world.distributed:
+            all_reduce_(ext, self.world, op=tdist.ReduceOp.MAX)
+        n_max, n_min = int(ext[0].item()), -float(ext[1].item())
+        if n_max <= 0:
+            raise ValueError(f"{what}: no client holds a record")
+        self.dp_q_max = min(1.0, t.batch_size / n_min)
+        # local steps charged per round: the most any client can run (local_steps, or local_epochs x ceil(n_max / B))
+        self.dp_round_steps = int(t.local_steps) if t.local_steps > 0 else \
+            int(t.local_epochs) * int(math.ceil(n_max / t.batch_size))
+        self.adapter.trainer.dpsgd = {"clip": float(p.clip_norm), "sigma": float(p.noise_multiplier),
+                                      "seed": self.noise_seed, "nmax": n_max}
+
+    def _dpsgd_tables(self, r: int, ids: list) -> dict:
+        """Round r's per-client DP-SGD noise keys ``philox_key(noise_seed, 'dpsgd_noise', r, client)`` as an ``extra``
+        table [K, 2]: they travel with the round's upload and reach the engine from the device table."""
+        if not (self.record_dp and ids):
+            return {}
+        from ..utils.seeding import philox_keys
+        return {"dpsgd_keys": torch.tensor(philox_keys(self.noise_seed, ("dpsgd_noise", r), ids), dtype=torch.int64)}
 
     # ------------------------------------------------------------------ eval
     @torch.no_grad()
@@ -261,7 +322,8 @@ class FederatedRunner:
         if r >= self.cfg.train.num_rounds or not hasattr(self.adapter.trainer, "prepare_round"):
             return
         st = self._round_setup(r)
-        pre = self.adapter.trainer.prepare_round(self.store, st["local_alive"], r)
+        dpx = self._dpsgd_tables(r, [self.local_ids[i] for i in st["local_alive"]])
+        pre = self.adapter.trainer.prepare_round(self.store, st["local_alive"], r, **({"extra": dpx} if dpx else {}))
         self._pre = (r, st, pre)
         self.prefetches += 1
 
@@ -287,14 +349,16 @@ class FederatedRunner:
         # distributed DP: each client's share of the noise is N(0, sigma^2 C^2 / m) for the round's m live participants
         # (public: every rank knows the participant set and the dropouts), so the SecAgg sum carries exactly sigma C
         dp_mode = getattr(p, "noise_mode", "local")
-        dp_scale = noise_scale(dp_mode, len(participants) - len(dropped)) if (p.dp and dp_mode != "local") else None
+        dp_scale = noise_scale(dp_mode, len(participants) - len(dropped)) if (self.client_dp and dp_mode != "local") \
+            else None
         epi = self.epilogue
         fast = epi is not None
         trainer = self.adapter.trainer
         if fast:
             # the round epilogue on the device (fl/epilogue.py), run by the trainer right after the local steps and
             # captured with them into the round's hipGraph; post (collective + apply) too when the ranks agreed on it
-            extra = epi.begin_round(r, ids, self.params, participants, dropped, dp_scale)
+            extra = {**epi.begin_round(r, ids, self.params, participants, dropped, dp_scale),
+                     **self._dpsgd_tables(r, ids)}
             with self.timer.phase("local_train"):
                 res = trainer.run_round(self.store, local_alive, self.params, r, epilogue=epi, extra=extra or None,
                                         post=epi.post if self.graph_comm else None)
@@ -303,7 +367,8 @@ class FederatedRunner:
         else:
             with self.timer.phase("local_train"):
                 res = trainer.run_round(self.store, local_alive, self.params, r,
-                                        **({"pre": pre} if pre is not None else {}))
+                                        **({"pre": pre} if pre is not None else {}),
+                                        **({"extra": self._dpsgd_tables(r, ids)} if self.record_dp else {}))
             with self.timer.phase("aggregate"):
                 if t.weighting == "uniform":
                     w = torch.ones(len(local_alive), dtype=torch.float64, device=dev)
@@ -379,7 +444,13 @@ class FederatedRunner:
                 self._set_params(self.aggregator.apply(self.params, mean_upd, wsum=wsum))
         if not fast and self.n_norm_slots:
             norms, metrics = metrics[5:], metrics[:5]
-        if p.dp:
+        if self.record_dp:
+            # record-level DP-SGD: every local step of a client is one subsampled-Gaussian step on its records at
+            # rate q_k <= q_max; a record sits in one client's shard, so the round costs that client's steps, charged
+            # at the most any client runs.  Conservative: the amplification by client sampling (a record's client
+            # takes part in a round with probability client_fraction only) is ignored.
+            self.accountant.step(self.dp_q_max, p.noise_multiplier, self.dp_round_steps)
+        elif p.dp:
             # the subsampled-Gaussian RDP bound holds for Poisson sampling at rate q; a fixed-size subset
             # drawn without replacement is accounted conservatively with no amplification (q = 1)
             q = min(1.0, t.client_fraction) if self.poisson else 1.0
@@ -391,7 +462,12 @@ class FederatedRunner:
                "comm_bytes_per_rank": int(comm_bytes),
                "upload_bytes": int(len(participants) - len(dropped)) * (self.P + 1) * 4}
         if p.dp:
-            rec["epsilon"] = self.accountant.get_epsilon(p.delta)
+            rec["epsilon"] = self.accountant.get_epsilon(p.delta)      # per client, or per record (dp_level)
+        if self.record_dp:
+            rec["dp_level"] = "record"
+            # records dropped from over-full Poisson lots on this rank's clients (BatchPlan._plan_poisson: a round
+            # that drops one is outside the accounted mechanism; 0 in practice)
+            rec["dp_lot_overflow"] = int(res.get("dp_lot_overflow", 0))
         return self.resolve_record(rec) if sync else rec
 
     def _set_params(self, new: torch.Tensor) -> None:

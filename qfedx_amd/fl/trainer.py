@@ -11,6 +11,8 @@ fixes the step count for every client (benchmarks).
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 from typing import Optional
 
@@ -67,9 +69,16 @@ class BatchPlan:
 
     def __init__(self, counts: torch.Tensor, client_ids: list, batch_size: int, round_num: int,
                  seed: int, local_epochs: int = 1, local_steps: int = 0, shuffle: bool = True,
-                 native: bool | None = None):
+                 native: bool | None = None, poisson: Optional[dict] = None):
+        """``poisson`` = dict(seed[, nmax][, bcap]): Poisson lots for record-level DP-SGD (``_plan_poisson``) instead
+        of minibatches in epoch order."""
         self.B = batch_size
         self.local_steps = local_steps
+        self.lot = batch_size          # the nominal batch / lot size (``B`` is the tables' width)
+        self.overflow = 0
+        if poisson is not None:
+            self._plan_poisson(counts, client_ids, batch_size, round_num, poisson, local_epochs, local_steps)
+            return
         C = _native_runtime() if native is not False else None
         if native and C is None:
             raise RuntimeError("native round scheduler requested but the extension is not built")
@@ -82,6 +91,61 @@ class BatchPlan:
             self.max_steps = int(self.idx.shape[0])
         else:
             self._plan_torch(counts, client_ids, batch_size, rk, local_epochs, local_steps, shuffle)
+
+    def _plan_poisson(self, counts, client_ids, B, round_num, poisson: dict, local_epochs, local_steps):
+        """Poisson lots (record-level DP-SGD, the sampling the subsampled-Gaussian accountant assumes): at every step
+        each record of client k enters the lot independently with probability q_k = min(1, B / n_k).
+
+        The lot is part of the mechanism, so it is keyed by the secret ``poisson['seed']`` (the noise seed), as
+        participant sampling is under DP: record i of client k is in the lot of step s when uniform i of the stream
+        ``philox_key(seed, 'dpsgd_lot', round, client, s)`` is <= q_k - nothing else enters, so the tables are the same
+        whichever clients share a rank.  Step counts are the usual ones (``local_steps``, or ``local_epochs`` x
+        ceil(n_k / B)).
+
+        The tables keep a static width ``Bcap = lot_width(B, nmax)`` = min(nmax, B + ceil(6 sqrt(B))) (``nmax``: the
+        largest shard of the run, default the largest given), so a captured round graph keeps one shape.  A lot larger
+        than Bcap keeps its Bcap records of lowest keyed priority (stream 1 of the same key) and the rest are counted in
+        ``overflow`` (round record: ``dp_lot_overflow``).  The accountant does NOT cover a round that overflowed: a
+        truncated lot is not a Poisson sample (a record's inclusion then depends on the others').  A lot's size is
+        Binomial(n_k, q_k) with mean <= B and standard deviation < sqrt(B), so the cap sits 6 standard deviations
+        above the mean: about 1e-9 per (client, step) by the normal approximation, and at most
+        exp(-18 B / (B + 2 sqrt(B))) by Bernstein's inequality.  ``poisson['bcap']`` overrides the width (tests).
+
+        Weights are 0 / 1 (``wts``), live records come first in a row, in priority order.  This vectorised host
+        planner is the only one for this mode: the native scheduler (csrc/runtime.cpp) plans epoch-order minibatches
+        only and is not consulted."""
+        from ..utils.seeding import philox_keys, philox_uniform_rows
+        K = len(client_ids)
+        n = counts.to(torch.int64).reshape(-1)
+        nb = (n + B - 1) // B
+        steps = torch.full((K,), local_steps, dtype=torch.int64) if local_steps > 0 else local_epochs * nb
+        self.steps_per_client = steps.tolist()
+        S = self.max_steps = int(steps.max()) if K else 0
+        N = max(int(n.max()) if K else 1, 1)
+        nmax = int(poisson.get("nmax") or N)
+        bcap = int(poisson["bcap"]) if poisson.get("bcap") else lot_width(B, nmax)
+        self.B = bcap
+        self.q = (float(B) / n.clamp(min=1).double()).clamp(max=1.0)
+        W = max(N, bcap)
+        active = torch.arange(S)[:, None] < steps[None, :]                       # [S, K]
+        if K == 0 or S == 0:
+            self.idx = torch.zeros(S, K, bcap, dtype=torch.int64)
+            self.wts = torch.zeros(S, K, bcap)
+            self.active = active.float()
+            return
+        keys = torch.tensor([kk for c in client_ids
+                             for kk in philox_keys(poisson["seed"], ("dpsgd_lot", round_num, int(c)), range(S))],
+                            dtype=torch.int64)                                   # [K * S, 2]
+        u = philox_uniform_rows(keys, W, 0).reshape(K, S, W)
+        pri = philox_uniform_rows(keys, W, 1).reshape(K, S, W).double()
+        inside = torch.arange(W)[None, None, :] < n[:, None, None]
+        sel = (u.double() <= self.q[:, None, None]) & inside & active.t()[:, :, None]
+        order = torch.argsort(torch.where(sel, pri, torch.full_like(pri, 2.0)), dim=-1, stable=True)[..., :bcap]
+        kept = sel.gather(-1, order)
+        self.overflow = int(sel.sum() - kept.sum())
+        self.idx = torch.where(kept, order, torch.zeros_like(order)).permute(1, 0, 2).contiguous()
+        self.wts = kept.float().permute(1, 0, 2).contiguous()
+        self.active = active.float()
 
     def _plan_torch(self, counts, client_ids, B, rk, local_epochs, local_steps, shuffle):
         K = len(client_ids)
@@ -143,6 +207,11 @@ class BatchPlan:
         self.active = active.float()
 
 
+def lot_width(batch_size: int, nmax: int) -> int:
+    """Static table width of Poisson lots: min(nmax, B + ceil(6 sqrt(B))) (``BatchPlan._plan_poisson``)."""
+    return max(1, min(int(nmax), int(batch_size) + int(math.ceil(6.0 * math.sqrt(batch_size)))))
+
+
 def graph_bucket(k: int, k_max: int) -> int:
     """Captured client count for ``k`` participating clients: the next power of two up to 8, then the next
     multiple of 8, capped at the rank's client count ``k_max``.  Under Poisson client sampling the per-round
@@ -186,7 +255,8 @@ def _native_runtime():
     return _NATIVE[0]
 
 
-def round_tables(store: ShardStore, local_idx: list, cfg, round_num: int, *extras, P: int = 0, device="cpu"):
+def round_tables(store: ShardStore, local_idx: list, cfg, round_num: int, *extras, P: int = 0, device="cpu",
+                 poisson: Optional[dict] = None):
     """A round's host side for clients ``store[local_idx]``: ``(plan, tables, common)`` - the keyed minibatch plan,
     the host tables the round uploads (store slots, minibatch indices, loss weights, step masks, valid samples,
     FedAvg sample-count weights, then every per-client [K, ...] table of ``extras``) and the host fields every round
@@ -200,10 +270,13 @@ def round_tables(store: ShardStore, local_idx: list, cfg, round_num: int, *extra
                             "steps": 0, "client_ids": [], "n_samples": torch.zeros(0, dtype=torch.float64)}
     li = torch.tensor(local_idx, dtype=torch.int64)
     cids = [store.client_ids[i] for i in local_idx]
-    plan = BatchPlan(store.counts[li], cids, cfg.batch_size, round_num, cfg.seed, cfg.local_epochs, cfg.local_steps)
+    plan = BatchPlan(store.counts[li], cids, cfg.batch_size, round_num, cfg.seed, cfg.local_epochs, cfg.local_steps,
+                     poisson=poisson)
     nvalid = (plan.wts > 0).sum(-1).float() * plan.active
     common = {"samples": float(nvalid.sum()), "steps": int(sum(plan.steps_per_client)), "client_ids": cids,
               "n_samples": store.counts[li].to(torch.float64)}
+    if poisson is not None:
+        common["dp_lot_overflow"] = plan.overflow       # records dropped from over-full lots (this rank's clients)
     if plan.idx.numel() and int(plan.idx.max()) >= max(1, store.nmax):   # the gather kernel trusts the table
         raise RuntimeError("minibatch plan indexes past the client store")
     tabs = {"lid": li, "idx": plan.idx, "wts": plan.wts, "act": plan.active, "nvalid": nvalid,
@@ -242,6 +315,10 @@ class VQCClientTrainer:
         self.capture_fallbacks = 0
         self.prefetch_hits = 0
         self._graph_cache = GraphLRU(_GRAPH_LRU)
+        # record-level DP-SGD (privacy.level=record; set by the runner): dict(clip, sigma, seed[, nmax]) - every local
+        # step draws a Poisson lot (BatchPlan._plan_poisson) and asks the engine for the clipped, noised lot gradient
+        # (VQCEngine.loss_and_grads(dpsgd=...)); the clients' noise keys ride in the round's tables as ``dpsgd_keys``
+        self.dpsgd: Optional[dict] = None
 
     def encode(self, X: torch.Tensor) -> torch.Tensor:
         return self.spec.encode_features(X)
@@ -324,7 +401,11 @@ class VQCClientTrainer:
         fj = None
         # the round epilogue's FedAvg as a ``fed_tail`` for the last step's engine call (the MFMA engine folds it into
         # its fused Adam epilogue); ``ctx.fed_done`` tells the epilogue's reduce that the engine ran it
-        make = getattr(epilogue, "fused_tail", None) if (fused and method == "adjoint") else None
+        dp = self.dpsgd
+        if dp is not None and float(dp["sigma"]) > 0 and "dpsgd_keys" not in dv:
+            raise ValueError("a record-level DP-SGD round needs the clients' noise keys (extra table 'dpsgd_keys')")
+        # (a DP-SGD step has no fused Adam, hence no FedAvg tail: the epilogue's reduce runs it)
+        make = getattr(epilogue, "fused_tail", None) if (fused and method == "adjoint" and dp is None) else None
         ft = make(dict(dv, loss=loss_all, correct=correct_all), theta, ctx) if make is not None else None
         if upfront:
             m, v, t = opt.init_state()
@@ -363,6 +444,16 @@ class VQCClientTrainer:
                 init = xb if spec.amplitude else None
                 xang = self.encode(xb)
             xang = self.engine.augment(xang, traj_keys, s)
+            if dp is not None:
+                # the lot's clipped, noised gradient; the keys are the round's device table (never a host scalar a
+                # captured graph would freeze), the step index is the captured launch's own
+                res = self.engine.loss_and_grads(xang, yb, ws, params, method, step=s, out_loss=loss_all[s],
+                                                 out_correct=correct_all[s], init=init,
+                                                 shared_frags=fj[1] if (fj is not None and s == 0) else None,
+                                                 dpsgd={"clip": dp["clip"], "sigma": dp["sigma"], "step": s,
+                                                        "keys": dv.get("dpsgd_keys"), "lot": cfg.batch_size})
+                opt.step(params, res["grad"], act_d[s])
+                continue
             res = self.engine.loss_and_grads(xang, yb, ws, params, method, rng_keys=(cfg.seed, round_num, s),
                                              readout_keys=ro_keys, step=s, out_loss=loss_all[s],
                                              out_correct=correct_all[s], init=init, fused_opt=(opt, act_d[s]),
@@ -384,7 +475,10 @@ class VQCClientTrainer:
         pre = RoundPrefetch(round_num, list(local_idx))
         if len(local_idx) == 0:
             return pre
-        plan, tabs, pre.common = round_tables(store, local_idx, cfg, round_num, extra)
+        lots = None
+        if self.dpsgd is not None:
+            lots = {"seed": self.dpsgd["seed"], "nmax": self.dpsgd.get("nmax")}
+        plan, tabs, pre.common = round_tables(store, local_idx, cfg, round_num, extra, poisson=lots)
         pre.plan, pre.tabs, pre.cids = plan, tabs, pre.common["client_ids"]
         pre.method = "spsa" if cfg.optimizer == "spsa" else cfg.grad_method
         fused = self.backend == "hip" and store.X.is_cuda

@@ -222,7 +222,7 @@ class VQCEngine:
                        rng_keys: tuple = (0,), readout_keys: Optional[torch.Tensor] = None,
                        step: int = 0, out_loss: Optional[torch.Tensor] = None,
                        out_correct: Optional[torch.Tensor] = None, init: Optional[torch.Tensor] = None,
-                       fused_opt=None, shared_frags=None, fed_tail=None) -> dict:
+                       fused_opt=None, shared_frags=None, fed_tail=None, dpsgd: Optional[dict] = None) -> dict:
         """Loss [K], gradient [K,P], correct [K] for [K,B] minibatches.  ``out_loss`` / ``out_correct``
         (optional [K] views, e.g. rows of a round buffer) receive the loss / hit counts in place.
         ``init`` = raw amplitudes [K,B,F<=2^n] or complex states (amplitude encoding; None otherwise).
@@ -231,9 +231,17 @@ class VQCEngine:
         ``shared_frags``: the MFMA engine's unitary fragments of this step, already built by the round prologue
         (``prologue_frag_job``; a round's first step only, when every client row is the global vector).
         ``fed_tail``: the round's FedAvg to fold into this (last) step's fused Adam epilogue (``QfxFedTail``); the
-        result says ``fed_done`` when the engine did."""
+        result says ``fed_done`` when the engine did.
+        ``dpsgd`` = dict(clip, sigma, keys [K, 2], step, lot): a record-level DP-SGD step - ``grad`` is the sum of
+        the live samples' gradients (``wmask > 0``), each clipped to l2 norm ``clip``, plus sigma clip z, over the
+        nominal lot size ``lot`` (``privacy/dp.py dpsgd_step_ref``); ``loss`` is the mean CE over the live samples.
+        The MFMA engine computes it from its per-sample gradient slab (csrc/hea_dpsgd.hip), the torch executor from
+        its per-sample gradients (adjoint, autograd); every other engine / method raises ``ValueError``."""
         spec = self.spec
         self._check(xang, init)
+        if dpsgd is not None:
+            return self._dpsgd(xang, y, wmask, params, method, readout_keys, step, out_loss, out_correct, init,
+                               shared_frags, dpsgd)
         if self.backend == "hip" and method == "adjoint":
             nz = self.noise if (self.noise is not None and self.noise.readout_noise) else None
             if fused_opt is not None and getattr(self.hip, "fuses_optimizer", False):
@@ -250,6 +258,76 @@ class VQCEngine:
             out_correct.copy_(res["correct"])
             res["correct"] = out_correct
         return res
+
+    # ------------------------------------------------------------------ record-level DP-SGD
+    def _dpsgd(self, xang, y, wmask, params, method, readout_keys, step, out_loss, out_correct, init, shared_frags,
+               dpsgd: dict) -> dict:
+        """``loss_and_grads(dpsgd=...)``: the MFMA engine's device reductions, or on the torch executor the float64
+        reference ``dpsgd_step_ref`` fed with its per-sample gradients."""
+        what = "record-level DP-SGD (privacy.level=record)"
+        if self.noise is not None:
+            raise ValueError(f"{what} needs a noiseless simulator (noise.kind=none)")
+        if method not in ("adjoint", "autograd") or (method == "autograd" and self.backend != "torch"):
+            raise ValueError(f"{what} needs train.grad_method=adjoint (or autograd on the torch backend), got "
+                             f"{method!r}: param_shift and spsa form no per-sample gradients")
+        if self.backend == "hip":
+            if not hasattr(self.hip, "_dpsgd_step"):
+                raise ValueError(f"{what} runs on the MFMA statevector engine (model.state_dtype=mfma | fp16 | "
+                                 "mfma_bf16 for the circuits hea_plan.eligible* accept) or on the torch backend; the "
+                                 "VALU pass engine keeps no per-sample gradients")
+            return self.hip.loss_and_grads(xang, y, wmask, params, self.spec, None, readout_keys, step, out_loss,
+                                           out_correct, init, shared_frags=shared_frags, dpsgd=dpsgd)
+        if self.backend != "torch":
+            raise ValueError(f"{what} is not implemented for model.simulator={self.backend}")
+        from ..privacy.dp import dpsgd_step_ref
+        live = (wmask > 0)
+        g, nll, hit, expz = self._per_sample_grads(xang, y, live, params, method, init)
+        ref = dpsgd_step_ref(g, live, dpsgd["clip"], dpsgd["sigma"], dpsgd.get("keys"), int(dpsgd.get("step", 0)),
+                             dpsgd["lot"])
+        n = live.sum(-1).to(nll.dtype)
+        res = {"loss": ((nll * live).sum(-1) / n.clamp(min=1)).float(), "grad": ref["grad"].to(params.dtype),
+               "correct": (hit & live).sum(-1).float(), "expz": expz.float(), "dp_norm": ref["norm"], "dp_c": ref["c"]}
+        if out_loss is not None:
+            out_loss.copy_(res["loss"])
+            res["loss"] = out_loss
+        if out_correct is not None:
+            out_correct.copy_(res["correct"])
+            res["correct"] = out_correct
+        return res
+
+    def _per_sample_grads(self, xang, y, live, params, method: str, init=None):
+        """Every sample's raw gradient of its own cross entropy (rows outside ``live`` are zero) on the torch
+        executor -> (g [K, B, P_total] float64, nll [K, B], hit [K, B] bool, <Z> [K, B, C])."""
+        spec = self.spec
+        K, B, _ = xang.shape
+        P = spec.n_theta
+        if method == "autograd":
+            p = params.detach().clone().double().requires_grad_(True)
+            th, a, b = spec.split(p)
+            prog = TorchProgram(self.ops, self.coef, spec.n_qubits, params.device, torch.complex128)
+            st = self._states(init)
+            psi = prog.run(self._rows(xang.double(), th), state=None if st is None else st.reshape(K * B, -1).to(prog.dtype))
+            expz = prog.expz(psi, spec.readout).reshape(K, B, -1)
+            logits = logits_from_expz(expz, a, b)
+            nll = -torch.log_softmax(logits, -1).gather(-1, y.unsqueeze(-1)).squeeze(-1)
+            # one backward per batch column: client k's parameter row reaches only its own samples
+            g = torch.stack([torch.autograd.grad(nll[:, j].sum(), p, retain_graph=True)[0] for j in range(B)], 1)
+            g = g * live.unsqueeze(-1).to(g)
+            return g, nll.detach(), logits.argmax(-1) == y, expz.detach()
+        with torch.no_grad():
+            th, a, b = spec.split(params)
+            rows = self._rows(xang, th)
+            psi = self.prog.run(rows, state=self._init_rows(init))
+            expz = self.prog.expz(psi, spec.readout).reshape(K, B, -1).float()
+            logits = logits_from_expz(expz, a, b)
+            logp = torch.log_softmax(logits, -1)
+            nll = -logp.gather(-1, y.unsqueeze(-1)).squeeze(-1)
+            dlog = (logp.exp() - F.one_hot(y, expz.shape[-1]).to(logp)) * live.unsqueeze(-1).to(logp)
+            w = dlog * a.unsqueeze(-2)
+            gg = self.prog.adjoint_grads(rows, psi, w.reshape(K * B, -1), spec.readout)
+            gs = slot_grads(gg, self.ops, self.coef, self.n_slots)[:, :P].reshape(K, B, P)
+            g = torch.cat([gs.double(), (dlog * expz).double(), dlog.double()], -1)
+            return g, nll, logits.argmax(-1) == y, expz
 
     def _loss_and_grads(self, xang, y, wmask, params, method, spsa_c, rng_keys, readout_keys, step,
                         init=None) -> dict:

@@ -797,6 +797,51 @@ class HeaMfmaProgram:
                               adam[0] + [cnt], adam[1], ro, self.C, self.n_theta, f.get("fed"),
                               bool(f.get("wrap", False)), int(f.get("n_norms", 0)))
 
+    def _dpsgd_step(self, x, p, yy, ww, K, B, loss, correct, grad, expz, noise, dpsgd, dbg=None, shared_frags=None,
+                    psi0=None) -> dict:
+        """One record-level DP-SGD step (csrc/hea_dpsgd.hip): the forward and adjoint passes of an ordinary step with
+        0 / 1 sample weights - so a slab row is that sample's raw gradient - and the per-sample readout records of
+        ``hea_readout_rec`` whatever the sample count; then ``hea_dp_norm`` (per-sample norm and clip factor) and
+        ``hea_dp_reduce`` (clipped lot sum + sigma C z from the clients' device key table, over the nominal lot) in
+        place of ``hea_grad_reduce``.  No circuit is evaluated twice.  ``ww``: a sample is live where its weight is
+        positive.  Readout noise is refused: the readout / CE kernel route writes no per-sample record."""
+        if noise is not None:
+            raise ValueError("record-level DP-SGD on the MFMA engine needs a noiseless readout (noise.kind / readout "
+                             "noise write no per-sample record)")
+        if not self.grad_cover_exact or self.n_gradops == 0 or p.shape[1] != self.n_theta + 2 * self.C:
+            raise ValueError("record-level DP-SGD needs every circuit parameter owned by exactly one gradient record "
+                             "and parameter rows [n_theta + 2 C]")
+        clip, sigma, lot = float(dpsgd["clip"]), float(dpsgd["sigma"]), float(dpsgd["lot"])
+        if not (clip > 0 and sigma >= 0 and lot > 0):
+            raise ValueError("dpsgd needs clip > 0, sigma >= 0 and lot > 0")
+        kk = dpsgd.get("keys")
+        if sigma > 0:
+            if kk is None or tuple(kk.shape) != (K, 2):
+                raise ValueError("dpsgd noise needs the clients' Philox keys as a [K, 2] table")
+            kk = kk.to(self.device).long().contiguous()      # (a device table already on the round path: no copy)
+        else:
+            kk = _NO_KEYS
+        C = ext()
+        S = K * B
+        live = (ww > 0).float()
+        shared = shared_frags is not None
+        fr = shared_frags if shared else self._frags(p, K)
+        part = self._buf("part", S * self.tiles_last * self.C, torch.float32)
+        wread = self._buf("wread", S * self.C, torch.float32)
+        gslab = self._buf("gslab", S * self.slab_tiles * self.n_gradops * 32, torch.int64)
+        rec = self._buf("rorec", S * (2 * self.C + 2), torch.float32)
+        norm = self._buf("dpnorm", S, torch.float64)
+        cfac = self._buf("dpc", S, torch.float64)
+        stored = self._forward(x, p, fr, K, B, part, store_last=True, dbg=dbg, shared=shared, psi0=psi0)
+        C.hea_readout_rec(part, self.tiles_last, self.C, B, K, yy, live, p, self.n_theta, expz, wread, rec)
+        self._adjoint(x, p, fr, K, B, stored, wread, gslab, dbg=dbg, shared=shared)
+        C.hea_dp_norm(gslab, self.slab_tiles, self.n_gradops, self.gmeta, B, K, p, rec, self.C, self.n_theta, clip,
+                      norm, cfac)
+        C.hea_dp_reduce(gslab, self.slab_tiles, self.n_gradops, self.gmeta, B, K, p, rec, live, cfac, self.C,
+                        self.n_theta, kk, int(dpsgd.get("step", 0)), sigma, clip, lot, grad, loss, correct)
+        return {"loss": loss, "grad": grad, "correct": correct, "expz": expz.reshape(K, B, self.C),
+                "dp_norm": norm.view(K, B), "dp_c": cfac.view(K, B)}
+
     def stamp_buffers(self) -> dict:
         """Zeroed stall-attribution buffers, one per pass launch (``fwd{j}``, ``adj{j}``), for the stamps build
         (``QFEDX_STAMPS=1``, scripts/hea_stamps.py)."""
@@ -806,11 +851,13 @@ class HeaMfmaProgram:
 
     def loss_and_grads(self, xang, y, wmask, params, spec, noise=None, keys=None, step: int = 0, out_loss=None,
                        out_correct=None, init: torch.Tensor | None = None, fused_opt=None, dbg=None,
-                       shared_frags=None, fed_tail=None) -> dict:
+                       shared_frags=None, fed_tail=None, dpsgd=None) -> dict:
         """One adjoint training step (same contract as ``HipProgram.loss_and_grads``).
         ``fused_opt`` = (BatchedOptimizer, active): with params updated in place (a contiguous fp32 tensor) and HIP
         Adam, the optimizer step runs in the gradient reduction's epilogue and the result says ``opt_done``;
-        otherwise the caller steps the optimizer itself."""
+        otherwise the caller steps the optimizer itself.
+        ``dpsgd`` = dict(clip, sigma, keys, step, lot): a record-level DP-SGD step (``_dpsgd_step``): ``grad`` is the
+        clipped, noised lot gradient; never fused with the optimizer or the FedAvg tail (no ``opt_done``)."""
         x, p, K, B = self._prep(xang, params)
         psi0 = self._start(init, K, B)
         S = K * B
@@ -820,6 +867,8 @@ class HeaMfmaProgram:
         loss = torch.empty(K, dtype=torch.float32, device=self.device) if out_loss is None else out_loss
         correct = torch.empty(K, dtype=torch.float32, device=self.device) if out_correct is None else out_correct
         grad = torch.empty_like(p)
+        if dpsgd is not None:
+            return self._dpsgd_step(x, p, yy, ww, K, B, loss, correct, grad, expz, noise, dpsgd, dbg, shared_frags, psi0)
         adam = None
         # Fused only while the reduction has at most one block per CU.  Every block publishes its gradient entries
         # with one agent-scope release (an L2 writeback here): at 16q x 64 clients (832 blocks) the fused launch took

@@ -9,6 +9,11 @@ rank 0 and broadcast, held in memory only - never written to the config, metrics
 or checkpoints.  Keying the noise by the public ``train.seed`` would let anyone holding the config
 and successive released models regenerate and subtract it, voiding the accountant's epsilon; that
 mode exists only behind ``privacy.deterministic_noise`` (tests of rank-count invariance / resume).
+
+``privacy.level: record`` moves the mechanism into the local steps (record-level DP-SGD): ``dpsgd_step_ref`` is its
+float64 reference - per-example clipping, noise on the lot sum, keyed by (noise_seed, 'dpsgd_noise', round, client)
+with element step P + i for parameter i of local step ``step`` - and the oracle of the device reductions
+(``csrc/hea_dpsgd.hip``); the aggregator then adds nothing (docs/ARCHITECTURE.md "Record-level DP-SGD").
 """
 from __future__ import annotations
 
@@ -54,6 +59,38 @@ def noise_scale(mode: str, live: int) -> float:
     if mode == "distributed":
         return 1.0 / float(max(1, live)) ** 0.5
     raise ValueError(f"privacy.noise_mode must be local | distributed, got {mode!r}")
+
+
+def dpsgd_noise(P: int, key, step: int) -> torch.Tensor:
+    """The P standard normals of local step ``step`` of one client: elements step P .. step P + P - 1 of the stream
+    ``philox_normal`` draws from the client's key (``philox_key(noise_seed, 'dpsgd_noise', round, client)``) - what
+    ``philox_normal_at`` gives the device reduction element for element (csrc/hea_dpsgd.hip)."""
+    off = int(step) * int(P)
+    z = philox_normal(off % 4 + P, (int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF), 0, off // 4)
+    return z[off % 4:]
+
+
+def dpsgd_step_ref(per_sample_grads: torch.Tensor, live: torch.Tensor, clip: float, sigma: float, keys, step: int,
+                   lot: float) -> dict:
+    """Float64 reference of one record-level DP-SGD step (Abadi et al. 2016), and the test oracle of the device
+    reductions.  ``per_sample_grads`` [K, B, P]: every example's raw gradient; ``live`` [K, B]: which rows are in the
+    lot (> 0); ``keys`` [K, 2]: the clients' noise keys; ``lot``: the nominal lot size the sum is divided by.
+
+        norm_s = ||g_s||,  c_s = min(1, C / max(norm_s, 1e-12))       (the rule of ``clip_factors``)
+        grad_k = (sum_{s live} c_s g_s + sigma C z_k) / lot,  z_k = dpsgd_noise(P, keys[k], step)
+
+    ``sigma = 0`` draws nothing; an empty lot leaves sigma C z / lot.  -> grad [K, P], norm / c [K, B] (float64)."""
+    g = per_sample_grads.detach().double()
+    K, B, P = g.shape
+    on = (live.reshape(K, B) > 0).to(g)
+    norm = g.norm(dim=-1)
+    c = torch.clamp(float(clip) / torch.clamp(norm, min=1e-12), max=1.0)
+    tot = (g * (c * on).unsqueeze(-1)).sum(1)
+    if sigma > 0:
+        kk = torch.as_tensor(keys).reshape(K, 2).cpu().tolist()
+        z = torch.stack([dpsgd_noise(P, kk[k], step) for k in range(K)]).double().to(g.device)
+        tot = tot + float(sigma) * float(clip) * z
+    return {"grad": tot / float(lot), "norm": norm, "c": c}
 
 
 def clip_and_noise(deltas: torch.Tensor, clip_norm: float, noise_multiplier: float, seed: int,

@@ -31,6 +31,8 @@ PURPOSE = {
     "synthetic": 10,
     "spsa": 11,
     "client_drop": 12,
+    "dpsgd_lot": 13,
+    "dpsgd_noise": 14,
 }
 
 PHILOX_M0 = 0xD2511F53
