@@ -191,6 +191,19 @@ __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
   return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
 
+// cmul with every rounding written down, for code whose bits must not depend on what it is compiled next to (the
+// layer-1 generation of the first forward pass in the per-plan build: every per-plan kernel must generate the
+// interpreter's amplitudes).  The real part rounds a.y b.y and fuses a.x b.x; IM names the product the imaginary part
+// FUSES, the other one is rounded on its own.  Nothing is left for FMA contraction to choose, and it is off here anyway.
+enum { IM_XY = 0, IM_YX = 1 };
+template <int IM>
+__device__ __forceinline__ float2 cmul_pin(float2 a, float2 b) {
+#pragma clang fp contract(off)
+  const float re = __builtin_fmaf(a.x, b.x, -(a.y * b.y));
+  const float im = IM == IM_XY ? __builtin_fmaf(a.x, b.y, a.y * b.x) : __builtin_fmaf(a.y, b.x, a.x * b.y);
+  return make_float2(re, im);
+}
+
 __device__ __forceinline__ f4 mfma(uint4 a, uint4 b, f4 c) {
 #if QFX_HEA_BF16
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0,

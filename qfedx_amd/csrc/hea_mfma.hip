@@ -295,7 +295,14 @@ __device__ __forceinline__ void store_lam_il(const PA& a, uint32_t* dst, const u
 }
 
 // RZ(ph) RX(th) F(x)|0> for a layer-1 qubit
+// Per-plan build: every rounding is written down (one product rounded, the other fused, per component) - the forms the
+// ahead-of-time build contracts this code to (read from its assembly: tools/hea_gen_isa.py), so that a per-plan kernel
+// generates the interpreter's bits whatever it is compiled next to.  The ahead-of-time build keeps the plain expressions
+// and with them its object code.
 __device__ __forceinline__ void l1_factor(float x, float th, float ph, int feature, float2* w) {
+#ifdef QFX_HEA_SPEC
+#pragma clang fp contract(off)
+#endif
   float sa, ca;
   __sincosf(0.5f * x, &sa, &ca);
   float2 v0, v1;
@@ -312,12 +319,23 @@ __device__ __forceinline__ void l1_factor(float x, float th, float ph, int featu
   float s, c;
   __sincosf(0.5f * th, &s, &c);
   // RX: w0 = c v0 - i s v1 ; w1 = -i s v0 + c v1      (-i z = (z.y, -z.x))
+#ifdef QFX_HEA_SPEC
+  // (the c products are fused, the s products rounded)
+  const float2 w0 = make_float2(__builtin_fmaf(c, v0.x, s * v1.y), __builtin_fmaf(c, v0.y, -(s * v1.x)));
+  const float2 w1 = make_float2(__builtin_fmaf(c, v1.x, s * v0.y), __builtin_fmaf(c, v1.y, -(s * v0.x)));
+  float sp, cp;
+  __sincosf(0.5f * ph, &sp, &cp);
+  // RZ: w[0] = w0 (cp, -sp) rounds its sp products, w[1] = w1 (cp, sp) its cp products
+  w[0] = make_float2(__builtin_fmaf(cp, w0.x, sp * w0.y), __builtin_fmaf(cp, w0.y, -(sp * w0.x)));
+  w[1] = make_float2(__builtin_fmaf(-sp, w1.y, cp * w1.x), __builtin_fmaf(sp, w1.x, cp * w1.y));
+#else
   float2 w0 = make_float2(c * v0.x + s * v1.y, c * v0.y - s * v1.x);
   float2 w1 = make_float2(c * v1.x + s * v0.y, c * v1.y - s * v0.x);
   float sp, cp;
   __sincosf(0.5f * ph, &sp, &cp);
   w[0] = cmul(w0, make_float2(cp, -sp));
   w[1] = cmul(w1, make_float2(cp, sp));
+#endif
 }
 
 // LDS images, addressed by BYTE offsets that combine by XOR (each access is one XOR of per-lane constants):
@@ -1030,10 +1048,18 @@ __device__ __forceinline__ void fwd_pass(const PA& a, int bid) {
 
   // ---------------------------------------------------------------- initial psi tile
   if (a.gen) {
+#ifdef QFX_HEA_SPEC
+#pragma clang fp contract(off)
+#endif
     // Product state of layer 1: wave 0 computes every qubit's 2-vector (lane q) and, by a complex product over
     // the wave, the factor of the qubits outside the tile (their bits are fixed over the tile).  Then the two
     // half-index tables: each entry is a product of <= 7 factors, all read from LDS before the first multiply
     // (one LDS round trip instead of one per factor).
+    // The interpreter and every per-plan kernel must generate the same bits.  The ahead-of-time build compiles the
+    // plain products (cmul) and its compiler chooses what to fuse; the per-plan build names each product's
+    // roundings (cmul_pin, l1_factor) as that choice came out, which differs from site to site: the first five wave
+    // steps and table factors 2.. fuse a.y b.x in the imaginary part, the last wave step, table factors 0, 1 and the
+    // quads a.x b.y (tools/hea_gen_isa.py compares the two builds' dataflow; tests/test_gpu_hea_spec_gen.py the bits).
     if (wave == 0) {
       float2 w[2] = {make_float2(1.f, 0.f), make_float2(1.f, 0.f)};
       if (tid < a.n) {
@@ -1046,7 +1072,14 @@ __device__ __forceinline__ void fwd_pass(const PA& a, int bid) {
       const float2 w0 = w[0], w1 = w[1];
       float2 f = outq ? (((fixed >> (tid & 31)) & 1) ? w1 : w0) : make_float2(1.f, 0.f);
 #pragma unroll
-      for (int off = 1; off < 64; off <<= 1) f = cmul(f, make_float2(__shfl_xor(f.x, off, 64), __shfl_xor(f.y, off, 64)));
+      for (int off = 1; off < 64; off <<= 1) {
+#ifdef QFX_HEA_SPEC
+        const float2 g = make_float2(__shfl_xor(f.x, off, 64), __shfl_xor(f.y, off, 64));
+        f = off < 32 ? cmul_pin<IM_YX>(f, g) : cmul_pin<IM_XY>(f, g);
+#else   // (written as it always was: the ahead-of-time object code depends on it)
+        f = cmul(f, make_float2(__shfl_xor(f.x, off, 64), __shfl_xor(f.y, off, 64)));
+#endif
+      }
       if (tid == 0) outer_s = make_float2(a.scale * f.x, a.scale * f.y);
     }
     lds_barrier();
@@ -1065,7 +1098,11 @@ __device__ __forceinline__ void fwd_pass(const PA& a, int bid) {
       float2 v = lowt ? make_float2(1.f, 0.f) : outer_s;
 #pragma unroll
       for (int j = 0; j < JMAX; ++j)
+#ifdef QFX_HEA_SPEC
+        if (j < nj) v = j < 2 ? cmul_pin<IM_XY>(v, fac[j]) : cmul_pin<IM_YX>(v, fac[j]);
+#else
         if (j < nj) v = cmul(v, fac[j]);
+#endif
       if (lowt)
         tabA[i] = v;
       else
@@ -1090,7 +1127,11 @@ __device__ __forceinline__ void fwd_pass(const PA& a, int bid) {
       uint32_t* ow = (uint32_t*)&out[i];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
+#ifdef QFX_HEA_SPEC
+        const float2 v = cmul_pin<IM_XY>(tabA[((4 * qq + e) ^ h) & am], vb);
+#else
         const float2 v = cmul(tabA[((4 * qq + e) ^ h) & am], vb);
+#endif
         ow[e] = pack_h2(v.x, v.y);
       }
     }

@@ -79,6 +79,18 @@ def obs_load_default() -> bool:
     return os.environ.get("QFEDX_HEA_OBS_LOAD", "1" if OBS_LOAD_DEFAULT else "0") != "0"
 
 
+def spec_gen_default(unset: bool = False) -> bool:
+    """``QFEDX_HEA_SPEC_GEN`` = 1 / 0: the forward pass that generates the layer-1 product state (pass 0 of an angle
+    program) gets a per-plan kernel like every other pass / stays on the interpreter.  Both generate the same bits: the
+    per-plan build writes the generation's fp32 products with the interpreter's roundings (csrc/hea_common.h cmul_pin).  Read when a program is built
+    (``HeaMfmaProgram.spec_gen``); amplitude programs have no such pass.  Unset, the caller decides (``unset``): the
+    engine (ops/engine.py: training, evaluation, the benchmark) turns it on, ``SPEC_GEN_ENGINE``; a program built
+    directly keeps pass 0 on the interpreter unless it is asked (``spec_gen=True``), as ``spec_passes()`` has always
+    reported it for such a program."""
+    env = os.environ.get("QFEDX_HEA_SPEC_GEN", "")
+    return bool(unset) if env == "" else env != "0"
+
+
 def ring_fwd_from_adj() -> bool:
     """``QFEDX_HEA_RING_ADJ`` = 13 / 14: a ring program's forward runs the groups of its 2^13-tile plan on widened
     tiles, so the adjoint runs on 2^13 tiles (two workgroups per CU) / the forward runs its own 2^14 plan (fewer group
@@ -106,6 +118,11 @@ SPLIT_READOUT_MIN_SAMPLES = 128
 # knob-1 run below every parent run; 8 clients 0.255 -> 0.250, inside three spreads (0.016): a tie.  Compiled into the
 # one kernel a pass has, so not gated by sample count.
 OBS_LOAD_DEFAULT = True
+# The engine's programs run the generating forward pass per plan (spec_gen_default): bitwise the same results.
+# Measured, 16q x 3L, clients x 32 samples, ms per round parent -> knob 1, alternating x 3 on one box
+# (profiles/hea_spec_gen_ab.txt): 64 clients 1.583 -> 1.539 (3 x the parent's spread: 0.024, met; pass 0 itself 0.30 ->
+# 0.265 ms per dispatch); 8 clients 0.254 -> 0.247, inside three spreads (0.015).
+SPEC_GEN_ENGINE = True
 # Ring programs: forward on the 2^13 plan's grouping with a 2^13 adjoint (True) or native 2^14 groups with a 2^14
 # adjoint (False); 16q x 3L: 9 against 8 group ops, both in 3 passes.  Measured, clients x 32 samples, ms per step,
 # alternating x 3 on one box (profiles/hea_ring_plan_ab.txt): 64 clients 2.070 -> 2.021 (every run below every native
@@ -116,7 +133,7 @@ RING_FWD_FROM_ADJ = True
 
 class HeaMfmaProgram:
     def __init__(self, spec, device, tile_bits: int | None = None, adj_tile_bits: int | None = None,
-                 storage: str = "fp16", use_spec: bool | None = None):
+                 storage: str = "fp16", use_spec: bool | None = None, spec_gen: bool | None = None):
         """``storage``: fp16 (default) or bf16 (BASELINE config 2) amplitudes and unitary fragments
         (csrc/hea_mfma_bf16.hip: v_mfma_f32_16x16x32_bf16, fp32 accumulation; 2^-9 per-op state rounding)."""
         if storage not in ("fp16", "bf16"):
@@ -231,6 +248,8 @@ class HeaMfmaProgram:
         self.split_readout = split_readout_default()
         # the per-plan kernel of a pass that starts with the observable op seeds lambda in its tile load (spec_cfg)
         self.obs_at_load = obs_load_default()
+        # the pass that generates the layer-1 product state gets a per-plan kernel too (False: the interpreter)
+        self.spec_gen = spec_gen_default() if spec_gen is None else bool(spec_gen)
         if self.spec_requested:
             self.prepare_spec()
 
@@ -305,11 +324,7 @@ class HeaMfmaProgram:
         fwd, adj, keys = [-1] * self.n_passes, [-1] * self.n_passes, []
         try:
             for j, ((f, ff), (a, fa)) in enumerate(self._host_progs):
-                # The forward pass that generates the layer-1 product state stays on the interpreter: compiled per
-                # plan, its fp32 complex products came out different in the last bit on a share of the amplitudes (FMA
-                # contraction follows the surrounding code), and the two paths must agree bitwise.  An amplitude
-                # program has no such pass: its pass 0 loads staged states like every later pass.
-                if not self._gen(j) and j <= self.fwd_last and len(f):
+                if (self.spec_gen or not self._gen(j)) and j <= self.fwd_last and len(f):
                     fwd[j], k = C.hea_spec_prepare(False, f, ff, self.spec_cfg(j, False), JIT_CACHE, CSRC, ARCH)
                     keys.append(k)
                 if len(a):

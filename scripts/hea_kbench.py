@@ -22,6 +22,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--spec", type=int, choices=(0, 1), default=None,
                     help="1: per-plan pass kernels, 0: the interpreter (default: QFEDX_HEA_SPEC)")
+    ap.add_argument("--spec-gen", type=int, choices=(0, 1), default=1,
+                    help="1: the generating forward pass 0 per plan as the engine runs it, 0: on the interpreter")
     ap.add_argument("--entangler", choices=("chain", "ring", "none"), default="chain",
                     help="ring: QFEDX_HEA_RING_ADJ=13 | 14 selects the adjoint tiling (profiles/hea_ring_plan_ab.txt)")
     ap.add_argument("--precision", action="store_true", help="also report errors against the fp32 VALU engine")
@@ -33,7 +35,10 @@ def main():
 
     dev = torch.device("cuda", 0)
     spec = VQCSpec(args.qubits, args.layers, 3, entangler=args.entangler)
-    prog = HeaMfmaProgram(spec, dev, use_spec=None if args.spec is None else bool(args.spec))
+    import inspect
+    # (--spec-gen: forward pass 0, the layer-1 generation, per plan too; trees before that knob take no such argument)
+    kw = {"spec_gen": bool(args.spec_gen)} if "spec_gen" in inspect.signature(HeaMfmaProgram.__init__).parameters else {}
+    prog = HeaMfmaProgram(spec, dev, use_spec=None if args.spec is None else bool(args.spec), **kw)
     sf, sa = getattr(prog, "spec_fwd", None), getattr(prog, "spec_adj", None)   # (older trees: no per-plan kernels)
     K, B = args.clients, args.batch
     S = K * B
@@ -75,7 +80,8 @@ def main():
            # (fused: the last adjoint pass computes the readout, on the interpreter; split: hea_readout_rec + per plan)
            "readout_mode": prog.readout_mode(S) if hasattr(prog, "readout_mode") else None,
            # (QFEDX_HEA_OBS_LOAD: the per-plan last adjoint pass seeds lambda in its tile load)
-           "obs_at_load": getattr(prog, "obs_at_load", None)}
+           "obs_at_load": getattr(prog, "obs_at_load", None),
+           "spec_gen": getattr(prog, "spec_gen", None)}
 
     def timeit(fn, name, nbytes):
         fn()

@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--spec", type=int, choices=(0, 1), default=None,
                     help="1: per-plan pass kernels (compiled with the stamps), 0: the interpreter (default: QFEDX_HEA_SPEC)")
+    ap.add_argument("--spec-gen", type=int, choices=(0, 1), default=1,
+                    help="1: the generating forward pass 0 per plan as the engine runs it, 0: on the interpreter")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -51,7 +53,10 @@ def main():
     y = torch.randint(0, 3, (K, B), generator=g).to(dev)
     w = torch.full((K, B), 1.0 / B, device=dev)
     params = torch.stack([spec.init_params(k) for k in range(K)]).to(dev)
-    prog = HeaMfmaProgram(spec, dev, use_spec=None if args.spec is None else bool(args.spec))
+    import inspect
+    # (--spec-gen: forward pass 0, the layer-1 generation, per plan too; trees before that knob take no such argument)
+    kw = {"spec_gen": bool(args.spec_gen)} if "spec_gen" in inspect.signature(HeaMfmaProgram.__init__).parameters else {}
+    prog = HeaMfmaProgram(spec, dev, use_spec=None if args.spec is None else bool(args.spec), **kw)
     print(json.dumps({"spec": prog.spec_active, "spec_passes": prog.spec_passes(samples=K * B),
                       "readout_mode": prog.readout_mode(K * B),
                       # QFEDX_HEA_OBS_LOAD: the per-plan last adjoint pass seeds lambda in its tile load (phase LOAD,
