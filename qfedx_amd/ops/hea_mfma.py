@@ -10,6 +10,12 @@
     adjoint passes  (reverse pass order; per-workgroup gradient partials)
     hea_grad_reduce (fixed-order sum over each client's samples and tiles)
 
+Every pass, forward or adjoint, of every route (training step, DP-SGD step, ``expz``, ``vjp``, the parameter-shift
+branches) is launched by ``HeaMfmaProgram._launch``, which derives the kernel's flags from the buffers it is given.
+What the host launches is pinned without a GPU: tools/hea_launch_trace.py records every native call with its arguments
+(workspaces by name, pass tables by identity) and tests/test_hea_launch_trace.py compares them, and the sha256 of every
+table the constructor builds, with tests/golden/hea_launch_traces.json.
+
 It exposes the subset of ``HipProgram``'s interface the engine / trainer use (``expz``, ``vjp``,
 ``loss_and_grads``, ``private_workspace``), so ``VQCEngine(..., backend="hip", state_dtype="mfma")``
 swaps it in for circuits ``hea_plan.eligible`` accepts.  Amplitude-encoded circuits (``hea_plan.eligible_amplitude``)
@@ -24,13 +30,15 @@ from __future__ import annotations
 
 import contextlib
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
 
 from ._ext import ext
-from .hea_plan import (OP_APPLY, OP_APPLY2, OP_BACK, OP_BACK2, OP_GRAD2, OP_GRAD_L1, OP_READOUT, TILE_BITS, W_CODE, eligible,
-                       eligible_amplitude, eligible_ring, fo_table, obs_table, pass_programs, plan_pair, refusal)
+from .hea_plan import (OP_APPLY, OP_APPLY2, OP_BACK, OP_BACK2, OP_GRAD2, OP_GRAD_L1, OP_READOUT, TILE_BITS, W_CODE, W_SLOT,
+                       W_SLOT2, eligible, eligible_amplitude, eligible_ring, fo_table, obs_table, pass_programs, plan_pair,
+                       refusal)
 
 ADJ_TILE_BITS = 13   # adjoint tiles: 2^13 amplitudes x (psi, lambda) = 64 KB of LDS -> two workgroups per CU
 
@@ -40,7 +48,6 @@ _FEATURE = {"ry": 0, "rx": 1, "rz": 2, "amplitude": 0}      # (an amplitude prog
 def _frag_index(ops: np.ndarray) -> torch.Tensor:
     """Per op the unitary fragments it multiplies by (slot * 4 + 0: U, + 2: U^H; a pair op names its two groups'),
     -1 for none: int32 [nops, 2] (prefetch table)."""
-    from .hea_plan import OP_APPLY, OP_APPLY2, OP_BACK, OP_BACK2, W_CODE, W_SLOT, W_SLOT2
     out = np.full((len(ops), 2), -1, dtype=np.int32)
     for i, w in enumerate(ops):
         code = int(w[W_CODE])
@@ -55,28 +62,31 @@ def _frag_index(ops: np.ndarray) -> torch.Tensor:
     return torch.from_numpy(out).contiguous()
 
 
+def _knob(name: str, unset, on: str | None = None):
+    """Environment knob ``name``: ``unset`` while unset or empty, else whether it is not ``0`` (``on``: is that value)."""
+    env = os.environ.get(name, "")
+    return unset if env == "" else (env == on if on is not None else env != "0")
+
+
 def spec_default() -> bool:
     """Per-plan pass kernels (csrc/hea_spec.cpp) instead of the interpreter: on by default, ``QFEDX_HEA_SPEC=0`` selects
     the interpreter (docs/ARCHITECTURE.md section 1b).  ``QFEDX_DEBUG=1`` stays on the interpreter: the device checks
     validate the op records the per-plan build no longer reads."""
-    if os.environ.get("QFEDX_DEBUG", "0") == "1":
-        return False
-    return os.environ.get("QFEDX_HEA_SPEC", "1") != "0"
+    return os.environ.get("QFEDX_DEBUG", "0") != "1" and _knob("QFEDX_HEA_SPEC", True)
 
 
 def split_readout_default():
     """``QFEDX_HEA_SPLIT_RO`` = 1 / 0 forces the split-readout step on / off wherever it is possible
     (``HeaMfmaProgram.readout_mode``); unset (None): by sample count, ``SPLIT_READOUT_MIN_SAMPLES``.  ``0`` makes every
     step launch what it launched before the split route existed."""
-    env = os.environ.get("QFEDX_HEA_SPLIT_RO", "")
-    return None if env == "" else env != "0"
+    return _knob("QFEDX_HEA_SPLIT_RO", None)
 
 
 def obs_load_default() -> bool:
     """``QFEDX_HEA_OBS_LOAD`` = 1 / 0: the per-plan kernel of the last adjoint pass seeds lambda while it loads its
     tile and runs no observable op (csrc/hea_mfma.hip seed_tile_il) / keeps the op, i.e. compiles exactly the text it
     compiled before the seeding load existed.  Read when a program is built (``HeaMfmaProgram.obs_at_load``)."""
-    return os.environ.get("QFEDX_HEA_OBS_LOAD", "1" if OBS_LOAD_DEFAULT else "0") != "0"
+    return _knob("QFEDX_HEA_OBS_LOAD", OBS_LOAD_DEFAULT)
 
 
 def spec_gen_default(unset: bool = False) -> bool:
@@ -87,16 +97,14 @@ def spec_gen_default(unset: bool = False) -> bool:
     engine (ops/engine.py: training, evaluation, the benchmark) turns it on, ``SPEC_GEN_ENGINE``; a program built
     directly keeps pass 0 on the interpreter unless it is asked (``spec_gen=True``), as ``spec_passes()`` has always
     reported it for such a program."""
-    env = os.environ.get("QFEDX_HEA_SPEC_GEN", "")
-    return bool(unset) if env == "" else env != "0"
+    return _knob("QFEDX_HEA_SPEC_GEN", bool(unset))
 
 
 def ring_fwd_from_adj() -> bool:
     """``QFEDX_HEA_RING_ADJ`` = 13 / 14: a ring program's forward runs the groups of its 2^13-tile plan on widened
     tiles, so the adjoint runs on 2^13 tiles (two workgroups per CU) / the forward runs its own 2^14 plan (fewer group
     ops) and the adjoint runs on the same 2^14 tiles.  Default ``RING_FWD_FROM_ADJ``."""
-    env = os.environ.get("QFEDX_HEA_RING_ADJ", "")
-    return RING_FWD_FROM_ADJ if env == "" else env == "13"
+    return _knob("QFEDX_HEA_RING_ADJ", RING_FWD_FROM_ADJ, on="13")
 
 
 _SPEC_WARNED = False
@@ -129,6 +137,15 @@ SPEC_GEN_ENGINE = True
 # run), 8 clients 0.339 -> 0.332: the pass with the layer-1 gradient groups gains more from two workgroups per CU
 # (0.52 -> 0.40 ms) than the extra group op costs the other passes.
 RING_FWD_FROM_ADJ = True
+
+
+# passes[j] = (the forward plan's pass, its device tables, the adjoint program's tables, the adjoint plan's pass), tables =
+# (op records, per-op fragment prefetch indices, fragment-order table): tuples, so indexing and unpacking them works too
+PassTables = namedtuple("PassTables", "ops fidx fo")
+PassEntry = namedtuple("PassEntry", "fwd_pass fwd adj adj_pass")
+# what every pass launch of one host call takes: inputs, parameter rows, fragments, clients, batch, whether the fragments
+# are one shared set, the stamps build's per-pass buffers (stamp_buffers) or None
+_Call = namedtuple("_Call", "x params fr K B shared dbg")
 
 
 class HeaMfmaProgram:
@@ -166,21 +183,55 @@ class HeaMfmaProgram:
                                       adj_tile_bits, ring_fwd_from_adj())
         self.adj_plan = plan_a
         self.adj_tile_bits = plan_a.passes[0].t if plan_a.passes else tile_bits
-        C = ext()
         self.n_slots = self.plan.n_slots
-        self.passes = []
+        self._lower_plans()
+        self._build_slot_table()
+        self.slab_tiles = max(1 << (self.n - p.t) for p in plan_a.passes)
+        self.scale = float(1 << (self.n // 2))
+        self.feature = _FEATURE[spec.feature_map.lower()]
+        self._iempty = torch.empty(0, dtype=torch.int32, device=self.device)      # "no buffer" of a launch
+        self._fempty = torch.empty(0, dtype=torch.float32, device=self.device)
+        self._ws = {}
+        self._ps_budget = None
+        if self.device.type == "cuda":
+            self._shift_budget()      # query free HBM now, never inside a graph capture
+        # noiseless steps compute the readout in the first adjoint pass (profiles/r5_fused_readout_ab.txt: a tie at 64
+        # clients, -2.7% at 8); the readout kernel runs for readout noise - and for tests comparing the two (False).
+        # Larger steps compute the same values in a launch of their own ahead of the adjoint (readout_mode: split).
+        self.fused_readout = True
+        # knobs, read when the program is built.  Per-plan pass kernels or the interpreter:
+        self.spec_requested = spec_default() if use_spec is None else bool(use_spec)
+        # split-readout steps (readout_mode): None = by sample count, True / False = wherever possible / never
+        self.split_readout = split_readout_default()
+        # the per-plan kernel of a pass that starts with the observable op seeds lambda in its tile load (spec_cfg)
+        self.obs_at_load = obs_load_default()
+        # the pass that generates the layer-1 product state gets a per-plan kernel too (False: the interpreter)
+        self.spec_gen = spec_gen_default() if spec_gen is None else bool(spec_gen)
+        # per-plan pass kernels: compiled (or loaded from the cache) and their modules loaded here, never inside a
+        # stream capture
+        self.spec_fwd, self.spec_adj, self.spec_keys = [-1] * self.n_passes, [-1] * self.n_passes, []
+        self.spec_launches = self.interp_launches = 0      # pass launches that ran a per-plan kernel / the interpreter
+        if self.spec_requested:
+            self.prepare_spec()
+
+    def _lower_plans(self) -> None:
+        """Both plans -> per-pass programs and tables: ``passes``, ``_host_progs``, ``n_regions``, ``fwd_last``,
+        ``gmeta`` / ``n_gradops`` / ``grad_cover_exact``; every program is checked on the host (``hea_check_ops``)."""
         gmeta = []
-        fplan = self.plan
-        progs_f = pass_programs(fplan, [])
+        progs_f = pass_programs(self.plan, [])
+        progs_a = pass_programs(self.adj_plan, gmeta)
         # Forward passes after the last one that applies a unitary are identities on the state (they exist for
         # the adjoint's layer-1 gradient tiles, e.g. every pass of an L = 1 circuit): the forward stops at that
         # pass, reads out there, and later passes' stored outputs alias its output.
         applies = [j for j, (_, fwd, _) in enumerate(progs_f)
                    if any(int(w[W_CODE]) in (OP_APPLY, OP_APPLY2) for w in fwd)]
-        self.fwd_last = applies[-1] if applies else 0
-        J = len(progs_f)
-        progs_a = pass_programs(plan_a, gmeta)
+        self.fwd_last = R = applies[-1] if applies else 0
+        if R < len(progs_f) - 1:
+            pr, fr_ops, _ = progs_f[R]
+            fr_ops = np.concatenate([fr_ops, obs_table(self.plan, pr, OP_READOUT)[None]], 0)
+            progs_f = [(p, f if j < R else (fr_ops if j == R else f[:0]), a) for j, (p, f, a) in enumerate(progs_f)]
         self.n_gradops = len(gmeta)
+        self.gmeta = torch.tensor(gmeta, dtype=torch.int32).reshape(-1).to(self.device)
         # the fused Adam epilogue of hea_grad_reduce updates each parameter in the block that formed its gradient:
         # it needs every theta parameter owned by exactly one gradient record (else the separate Adam launch runs)
         owned = []
@@ -188,26 +239,25 @@ class HeaMfmaProgram:
             nr = int(row[1]) & 15
             owned += [int(v) for v in row[2:2 + nr]] + [int(v) for v in row[6:6 + nr]]
         self.grad_cover_exact = sorted(owned) == list(range(self.n_theta))
-        if self.fwd_last < J - 1:
-            pr, fr_ops, ar = progs_f[self.fwd_last]
-            fr_ops = np.concatenate([fr_ops, obs_table(fplan, pr, OP_READOUT)[None]], 0)
-            progs_f = [(p, f if j < self.fwd_last else (fr_ops if j == self.fwd_last else f[:0]), a)
-                       for j, (p, f, a) in enumerate(progs_f)]
+        self.passes = []
         self.n_regions = []       # per pass: gradient records of its adjoint program (LDS regions)
         self._host_progs = []     # per pass: host (ops, fidx) of the forward / adjoint programs (per-plan kernels)
+
+        def tables(ops, p, adjoint):
+            t, fidx = torch.from_numpy(ops.astype(np.int32)).contiguous(), _frag_index(ops)
+            ext().hea_check_ops(t, fidx, self.n_slots, self.n_theta, adjoint, p.t, self.n_gradops)
+            fo = torch.from_numpy(fo_table(ops, p, self.n).reshape(-1))
+            return (t, fidx), PassTables(t.to(self.device), fidx.to(self.device), fo.to(self.device))
         for (p, fwd, _), (pa, _, adj) in zip(progs_f, progs_a):
-            f = torch.from_numpy(fwd.astype(np.int32)).contiguous()
-            a = torch.from_numpy(adj.astype(np.int32)).contiguous()
-            ff, fa = _frag_index(fwd), _frag_index(adj)
-            C.hea_check_ops(f, ff, self.n_slots, self.n_theta, False, p.t, self.n_gradops)
-            C.hea_check_ops(a, fa, self.n_slots, self.n_theta, True, pa.t, self.n_gradops)
+            (hf, df), (ha, da) = tables(fwd, p, False), tables(adj, pa, True)
             self.n_regions.append(sum(2 if int(w[W_CODE]) in (OP_BACK2, OP_GRAD2) else
                                       int(int(w[W_CODE]) in (OP_BACK, OP_GRAD_L1)) for w in adj))
-            of = torch.from_numpy(fo_table(fwd, p, self.n).reshape(-1)).to(self.device)
-            oa = torch.from_numpy(fo_table(adj, pa, self.n).reshape(-1)).to(self.device)
-            self.passes.append((p, (f.to(self.device), ff.to(self.device), of),
-                                (a.to(self.device), fa.to(self.device), oa), pa))
-            self._host_progs.append(((f, ff), (a, fa)))
+            self.passes.append(PassEntry(p, df, da, pa))
+            self._host_progs.append((hf, ha))
+
+    def _build_slot_table(self) -> None:
+        """``slot_tab``: per unitary slot its qubit count and the theta indices of its rotations (hea_frags); every
+        parameter must be owned by a pass."""
         slot_tab = np.zeros((max(self.n_slots, 1), 9), dtype=np.int32)
         owner = np.zeros(self.n_theta, dtype=np.int32)
         for p in self.plan.passes:
@@ -224,34 +274,6 @@ class HeaMfmaProgram:
         if (owner == 0).any():
             raise RuntimeError("a parameter has no owning pass")
         self.slot_tab = torch.from_numpy(slot_tab).to(self.device)
-        self.gmeta = torch.tensor(gmeta, dtype=torch.int32).reshape(-1).to(self.device)
-        self.slab_tiles = max(1 << (self.n - p.t) for p in plan_a.passes)
-        self.scale = float(1 << (self.n // 2))
-        self.feature = _FEATURE[spec.feature_map.lower()]
-        self._ws = {}
-        self._ps_budget = None
-        # noiseless steps compute the readout in the first adjoint pass (profiles/r5_fused_readout_ab.txt: a tie at 64
-        # clients, -2.7% at 8); the readout kernel runs for readout noise - and for tests comparing the two (False).
-        # Larger steps compute the same values in a launch of their own ahead of the adjoint (readout_mode: split).
-        self.fused_readout = True
-        if self.device.type == "cuda":
-            self._shift_budget()      # query free HBM now, never inside a graph capture
-        # per-plan pass kernels: compiled (or loaded from the cache) and their modules loaded here, never inside a
-        # stream capture
-        self.spec_fwd = [-1] * len(self.passes)
-        self.spec_adj = [-1] * len(self.passes)
-        self.spec_keys = []
-        self.spec_launches = 0      # pass launches that ran a per-plan kernel / the interpreter (tests, tools)
-        self.interp_launches = 0
-        self.spec_requested = spec_default() if use_spec is None else bool(use_spec)
-        # split-readout steps (readout_mode): None = by sample count, True / False = wherever possible / never
-        self.split_readout = split_readout_default()
-        # the per-plan kernel of a pass that starts with the observable op seeds lambda in its tile load (spec_cfg)
-        self.obs_at_load = obs_load_default()
-        # the pass that generates the layer-1 product state gets a per-plan kernel too (False: the interpreter)
-        self.spec_gen = spec_gen_default() if spec_gen is None else bool(spec_gen)
-        if self.spec_requested:
-            self.prepare_spec()
 
     @property
     def spec_active(self) -> bool:
@@ -296,17 +318,14 @@ class HeaMfmaProgram:
         return -1 if computes_readout else self.spec_adj[j]
 
     def _count(self, handle: int) -> int:
-        if handle >= 0:
-            self.spec_launches += 1
-        else:
-            self.interp_launches += 1
+        self.spec_launches += handle >= 0
+        self.interp_launches += handle < 0
         return handle
 
     def spec_cfg(self, j: int, adjoint: bool) -> list:
         """Constants pass j's per-plan kernel is compiled with (hea_bindings.cpp spec_desc)."""
-        p = self.passes[j][3] if adjoint else self.passes[j][0]
-        J = self.n_passes
-        gen, load_lam, store_lam = (0, int(j < J - 1), int(j > 0)) if adjoint else (int(self._gen(j)), 0, 0)
+        p = self.passes[j].adj_pass if adjoint else self.passes[j].fwd_pass
+        gen, load_lam, store_lam = (0, int(j < self.n_passes - 1), int(j > 0)) if adjoint else (int(self._gen(j)), 0, 0)
         glo = os.environ.get("QFEDX_EXTRA_HIPFLAGS", "")
         gate_lo = 0 if "-DQFX_HEA_GATE_LO=0" in glo else (1 if "-DQFX_HEA_GATE_LO=1" in glo else -1)
         from .. import _build
@@ -379,7 +398,7 @@ class HeaMfmaProgram:
     @property
     def tiles_last(self) -> int:
         """Tiles per sample of the pass that reads out <Z> (the last forward pass that runs)."""
-        return 1 << (self.n - self.passes[self.fwd_last][0].t)
+        return 1 << (self.n - self.passes[self.fwd_last].fwd_pass.t)
 
     def _gen(self, j: int) -> bool:
         """Forward pass j generates the layer-1 product state in its tile (pass 0 of an angle program)."""
@@ -441,33 +460,46 @@ class HeaMfmaProgram:
         self._check_init(init)
         return self._stage(init, K, B, tag) if self.amplitude else None
 
+    def _launch(self, j: int, adjoint: bool, c: _Call, *, psi_in=None, psi_out=None, lam_in=None, lam_out=None,
+                wread=None, part=None, gslab=None, readout=None, in_rep: int = 1) -> None:
+        """Launch pass j, forward or adjoint: the only caller of ``hea_pass``.  The flags follow from the buffers given
+        (store psi: ``psi_out``; load / store lambda: ``lam_in`` / ``lam_out``; a forward pass generates its input iff
+        ``_gen(j)``, which must agree with an absent ``psi_in``); ``readout`` = [y, wts, expz, wread, rec]: an adjoint
+        pass that computes the fused readout from ``part``, on the interpreter (``_adj_handle``)."""
+        e = self.passes[j]
+        p, tab = (e.adj_pass, e.adj) if adjoint else (e.fwd_pass, e.fwd)
+        gen = not adjoint and self._gen(j)
+        if not adjoint and gen != (psi_in is None or psi_in.numel() == 0):
+            raise RuntimeError("forward pass without a start: amplitude programs need staged states")
+        geom = self._geom(p, gen, lam_in is not None, psi_out is not None, lam_out is not None, c.B, c.params.shape[1],
+                          c.K * c.B, c.x.shape[1], c.K, in_rep, self.n_regions[j] if adjoint else 0, c.shared)
+        handle = self._adj_handle(j, readout is not None) if adjoint else self.spec_fwd[j]
+        bufs = [self._iempty if t is None else t for t in (psi_in, psi_out, lam_in, lam_out)]
+        outs = [self._fempty if t is None else t for t in (wread, part, gslab)]
+        ext().hea_pass(adjoint, *tab, geom, self.scale, *bufs, c.x, c.params, c.fr, *outs,
+                       c.dbg[f"{'adj' if adjoint else 'fwd'}{j}"] if c.dbg else _NODBG,
+                       *(() if readout is None else (readout, self.tiles_last)), spec=self._count(handle))
+
     def _forward(self, x, params, fr, K, B, part, store_last: bool = False, tag: str = "", dbg=None,
-                 shared: bool = False, psi0=None):
-        """Forward passes up to the readout pass ``fwd_last``; returns the stored pass outputs (all of them with
+                 shared: bool = False, psi0=None, first: int = 0, in_rep: int = 1, pingpong: str = "pe"):
+        """Forward passes ``first``..``fwd_last`` (the readout pass); returns the stored pass outputs (all of them with
         ``store_last``: the adjoint starts each pass from its output; identity passes after ``fwd_last`` alias
-        its output).  ``tag`` names the workspaces; ``dbg`` (stamps build): per-pass stall-attribution buffers."""
-        C = ext()
-        S = K * B
-        N = S << self.n
-        stored = []
-        empty = torch.empty(0, dtype=torch.int32, device=self.device)
-        fempty = torch.empty(0, dtype=torch.float32, device=self.device)
+        its output).  ``psi0``: the input of pass ``first`` (none: it generates), each row of it read by ``in_rep``
+        consecutive samples.  ``tag`` names the workspaces, ``pingpong`` the two an evaluation alternates between;
+        ``dbg`` (stamps build): per-pass stall-attribution buffers."""
+        c = _Call(x, params, fr, K, B, shared, dbg)
+        N = (K * B) << self.n
+        stored, psi = [], psi0
         J, R = self.n_passes, self.fwd_last
-        for j in range(R + 1):
-            p, fwd = self.passes[j][0], self.passes[j][1]
-            keep = j < R or store_last
+        for j in range(first, R + 1):
             # evaluation only needs the previous pass output: two ping-pong buffers instead of one per pass
-            name = f"{tag}psi{j}" if store_last else f"{tag}pe{j % 2}"
-            out = self._buf(name, N, torch.int32) if keep else empty
-            psi_in = stored[-1] if j > 0 else (psi0 if psi0 is not None else empty)
-            if self._gen(j) != (psi_in.numel() == 0):
-                raise RuntimeError("forward pass without a start: amplitude programs need staged states")
-            geom = self._geom(p, self._gen(j), False, keep, False, B, params.shape[1], S, x.shape[1], K, shared=shared)
-            C.hea_pass(False, fwd[0], fwd[1], fwd[2], geom, self.scale, psi_in, out, empty, empty, x, params, fr, fempty,
-                       part if j == R else fempty, fempty, dbg[f"fwd{j}"] if dbg else _NODBG,
-                       spec=self._count(self.spec_fwd[j]))
-            if keep:
+            name = f"{tag}psi{j}" if store_last else f"{tag}{pingpong}{(j - first) % 2}"
+            out = self._buf(name, N, torch.int32) if j < R or store_last else None
+            self._launch(j, False, c, psi_in=psi, psi_out=out, part=part if j == R else None,
+                         in_rep=in_rep if j == first else 1)
+            if out is not None:
                 stored.append(out)
+            psi = out
         if store_last:
             stored += [stored[R]] * (J - 1 - R)
         return stored
@@ -477,29 +509,26 @@ class HeaMfmaProgram:
         """Adjoint passes, last pass first.  ``readout`` = (part, y, wts, expz, rec): the first adjoint pass computes
         every sample's readout and dL/d<Z> itself (fused readout; ``wread`` is then its output, read by the later
         passes) instead of taking ``wread`` from the readout kernel."""
-        C = ext()
-        S = K * B
-        N = S << self.n
-        empty = torch.empty(0, dtype=torch.int32, device=self.device)
-        fempty = torch.empty(0, dtype=torch.float32, device=self.device)
-        J = self.n_passes
-        lam_in = empty
-        for j in range(J - 1, -1, -1):
-            _, _, adj, p = self.passes[j]
-            lam_out = self._buf(f"{tag}lam{j % 2}", N, torch.int32) if j > 0 else empty
-            geom = self._geom(p, False, j < J - 1, False, j > 0, B, params.shape[1], S, x.shape[1], K,
-                              n_regions=self.n_regions[j], shared=shared)
-            if readout is not None and j == J - 1:
-                part, yy, ww, expz, rec = readout
-                C.hea_pass(True, adj[0], adj[1], adj[2], geom, self.scale, stored[j], empty, lam_in, lam_out, x,
-                           params, fr, fempty, part, gslab, dbg[f"adj{j}"] if dbg else _NODBG,
-                           [yy, ww, expz, wread, rec], self.tiles_last,
-                           spec=self._count(self._adj_handle(j, True)))
-            else:
-                C.hea_pass(True, adj[0], adj[1], adj[2], geom, self.scale, stored[j], empty, lam_in, lam_out, x,
-                           params, fr, wread, fempty, gslab, dbg[f"adj{j}"] if dbg else _NODBG,
-                           spec=self._count(self._adj_handle(j, False)))
+        c = _Call(x, params, fr, K, B, shared, dbg)
+        lam_in = None
+        for j in reversed(range(self.n_passes)):
+            lam_out = self._buf(f"{tag}lam{j % 2}", (K * B) << self.n, torch.int32) if j > 0 else None
+            ro = readout if j == self.n_passes - 1 else None
+            self._launch(j, True, c, psi_in=stored[j], lam_in=lam_in, lam_out=lam_out, gslab=gslab,
+                         wread=wread if ro is None else None, part=None if ro is None else ro[0],
+                         readout=None if ro is None else [*ro[1:4], wread, ro[4]])
             lam_in = lam_out
+
+    def _expect(self, x, th, K, B, z, tag: str = "", init=None, **fwd):
+        """Fragments of ``th``, the forward passes (``_forward`` keywords) and <Z> summed into ``z`` [K B, C], in
+        ``tag``'s workspaces -> (fragments, stored pass outputs).  ``init``: raw amplitudes to stage as the start."""
+        fr = self._frags(th, K, tag)
+        part = self._buf(f"{tag}part", K * B * self.tiles_last * self.C, torch.float32)
+        if init is not None:
+            fwd["psi0"] = self._stage(init, K, B, tag)
+        stored = self._forward(x, th, fr, K, B, part, tag=tag, **fwd)
+        ext().readout_sum(part, self.tiles_last, self.C, K * B, z)
+        return fr, stored
 
     def _prep(self, xang, params):
         K, B, F = xang.shape
@@ -538,13 +567,8 @@ class HeaMfmaProgram:
         Kc = max(1, min(K, self._shift_budget() // max(1, 2 * B * ((1 << self.n) * 4))))
         for k0 in range(0, K, Kc):
             k1 = min(K, k0 + Kc)
-            Sc = (k1 - k0) * B
-            thc = th[k0:k1] if Kc < K else th
-            fr = self._frags(thc, k1 - k0)
-            part = self._buf("part", Sc * self.tiles_last * self.C, torch.float32)
-            psi0 = self._stage(init[k0:k1], k1 - k0, B) if self.amplitude else None     # staged per client chunk
-            self._forward(x[k0 * B:k1 * B], thc, fr, k1 - k0, B, part, psi0=psi0)
-            ext().readout_sum(part, self.tiles_last, self.C, Sc, out[k0 * B * self.C:k1 * B * self.C])
+            self._expect(x[k0 * B:k1 * B], th[k0:k1] if Kc < K else th, k1 - k0, B, out[k0 * B * self.C:k1 * B * self.C],
+                         init=init[k0:k1] if self.amplitude else None)     # (staged per client chunk)
         if noise is not None:
             from .statevec_hip import _keys
             ext().readout_noise(out, self.C, B, S, noise.p01, noise.p10, noise.shots, _keys(keys, noise), int(step))
@@ -557,11 +581,8 @@ class HeaMfmaProgram:
         psi0 = self._start(init, K, B)
         th = self._pad_params(th)
         S = K * B
-        fr = self._frags(th, K)
-        part = self._buf("part", S * self.tiles_last * self.C, torch.float32)
-        stored = self._forward(x, th, fr, K, B, part, store_last=True, psi0=psi0)
         z = self._buf("expz", S * self.C, torch.float32)
-        ext().readout_sum(part, self.tiles_last, self.C, S, z)
+        fr, stored = self._expect(x, th, K, B, z, store_last=True, psi0=psi0)
         wr = w.reshape(S, self.C).float().contiguous()
         gslab = self._buf("gslab", S * self.slab_tiles * self.n_gradops * 32, torch.int64)
         self._adjoint(x, th, fr, K, B, stored, wr, gslab)
@@ -635,17 +656,13 @@ class HeaMfmaProgram:
         f0 = torch.empty(K, B, C, dtype=torch.float32, device=self.device)
         jac = torch.empty(K, B, C, P, dtype=torch.float32, device=self.device)
         fpi = torch.empty(K, P, B, C, dtype=torch.float32, device=self.device) if with_mean else None
-        empty = torch.empty(0, dtype=torch.int32, device=self.device)
         eye = torch.eye(C, dtype=torch.float32, device=self.device)
         for k0 in range(0, K, Kc):
             k1 = min(K, k0 + Kc)
             nk, S = k1 - k0, (k1 - k0) * B
             xs, ths = x[k0 * B:k1 * B], th[k0:k1].contiguous()
-            fr = self._frags(ths, nk, "ps")
-            part = self._buf("pspart", S * self.tiles_last * C, torch.float32)
-            stored = self._forward(xs, ths, fr, nk, B, part, store_last=True, tag="ps")
             z = self._buf("psz", S * C, torch.float32)
-            E.readout_sum(part, self.tiles_last, C, S, z)
+            fr, stored = self._expect(xs, ths, nk, B, z, "ps", store_last=True)
             f0[k0:k1] = z.view(nk, B, C)
             # per-sample Jacobian rows: one adjoint sweep per class over the stored forward, reduced with spc = 1
             gslab = self._buf("psgslab", S * self.slab_tiles * self.n_gradops * 32, torch.int64)
@@ -671,7 +688,7 @@ class HeaMfmaProgram:
                     a1 = min(nk, a0 + nkc)
                     for r0 in range(0, Pj, nr):
                         r1 = min(Pj, r0 + nr)
-                        src = stored[j - 1][(a0 * B) << n:(a1 * B) << n] if j > 0 else empty
+                        src = stored[j - 1][(a0 * B) << n:(a1 * B) << n] if j > 0 else None
                         zb = self._pi_branch(j, xs[a0 * B:a1 * B], ths[a0:a1], slots[r0:r1], B, src)
                         fpi[k0 + a0:k0 + a1].index_copy_(1, slots[r0:r1], zb)
         return f0, fpi, jac
@@ -709,7 +726,7 @@ class HeaMfmaProgram:
         kk = keys.to(self.device).long().contiguous() if (need_m and keys is not None) else _NO_KEYS.to(self.device)
         if need_m and keys is None:
             raise ValueError("shot sampling needs per-client Philox keys")
-        fe = torch.empty(0, device=self.device)
+        fe = self._fempty
         ext().ps_combine(f0 if need_m else fe, fpi if need_m else fe, jac.contiguous(), w.float().contiguous(), kk,
                          noise.p01 if noisy else 0.0, noise.p10 if noisy else 0.0, noise.shots if noisy else 0,
                          int(step), int(noisy), out)
@@ -719,32 +736,14 @@ class HeaMfmaProgram:
         """<Z> of theta + pi e_slot for clients ths [na, ps] x slots [nr] owned by forward pass j: passes
         j..fwd_last, the first reading the clients' stored pass j - 1 outputs ``src`` [na B 2^n] (each row
         shared by nr parameter rows: in_rep) or, for j = 0, regenerating the product state.  -> [na, nr, B, C]"""
-        E = ext()
         na, nr = ths.shape[0], slots.numel()
         Kr, S = na * nr, na * nr * B
         ps = ths.shape[1]
         thr = ths.repeat_interleave(nr, 0).view(na, nr, ps).clone()
         thr[:, torch.arange(nr, device=self.device), slots] += float(np.pi)
         thr = thr.view(Kr, ps).contiguous()
-        fr = self._frags(thr, Kr, "pb")
-        R = self.fwd_last
-        part = self._buf("pbpart", S * self.tiles_last * self.C, torch.float32)
-        N = S << self.n
-        empty = torch.empty(0, dtype=torch.int32, device=self.device)
-        fempty = torch.empty(0, dtype=torch.float32, device=self.device)
-        psi_in = src
-        for jj in range(j, R + 1):
-            p, fwd = self.passes[jj][0], self.passes[jj][1]
-            keep = jj < R
-            out = self._buf(f"pbpsi{(jj - j) % 2}", N, torch.int32) if keep else empty
-            first = jj == j
-            geom = self._geom(p, jj == 0, False, keep, False, B, ps, S, xs.shape[1], Kr, nr if first else 1)
-            E.hea_pass(False, fwd[0], fwd[1], fwd[2], geom, self.scale, psi_in, out, empty, empty, xs, thr, fr, fempty,
-                       part if jj == R else fempty, fempty, _NODBG,
-                       spec=self._count(self.spec_fwd[jj]))
-            psi_in = out
         z = self._buf("pbz", S * self.C, torch.float32)
-        E.readout_sum(part, self.tiles_last, self.C, S, z)
+        self._expect(xs, thr, Kr, B, z, "pb", psi0=src, first=j, in_rep=nr, pingpong="psi")
         return z.view(na, nr, B, self.C)
 
     # ------------------------------------------------------------------ train step
@@ -762,6 +761,21 @@ class HeaMfmaProgram:
             return None
         return [self.slot_tab, self._buf("pfrags", self.n_slots * 4 * 128 * 4, torch.int32)]
 
+    def _head(self, x, p, K, B, shared_frags, dbg, psi0):
+        """What a training step starts with: the fragments (the shared set or built from ``p``), the step's workspaces
+        and the stored forward -> (adjoint(readout=None): runs the adjoint passes over it, part, wread, gslab)."""
+        S = K * B
+        shared = shared_frags is not None
+        fr = shared_frags if shared else self._frags(p, K)
+        part = self._buf("part", S * self.tiles_last * self.C, torch.float32)
+        wread = self._buf("wread", S * self.C, torch.float32)
+        gslab = self._buf("gslab", S * self.slab_tiles * self.n_gradops * 32, torch.int64)
+        stored = self._forward(x, p, fr, K, B, part, store_last=True, dbg=dbg, shared=shared, psi0=psi0)
+
+        def adjoint(readout=None):
+            self._adjoint(x, p, fr, K, B, stored, wread, gslab, readout=readout, dbg=dbg, shared=shared)
+        return adjoint, part, wread, gslab
+
     def _step(self, x, p, yy, ww, K, B, loss, correct, grad, expz, noise, keys, step, adam=None, dbg=None,
               shared_frags=None, fed=None, psi0=None):
         """Forward, readout + CE, adjoint and gradient reduction of clients [0, K).
@@ -770,12 +784,7 @@ class HeaMfmaProgram:
         pass (``stamp_buffers``, stamps build only)."""
         C = ext()
         S = K * B
-        shared = shared_frags is not None
-        fr = shared_frags if shared else self._frags(p, K)
-        part = self._buf("part", S * self.tiles_last * self.C, torch.float32)
-        wread = self._buf("wread", S * self.C, torch.float32)
-        gslab = self._buf("gslab", S * self.slab_tiles * self.n_gradops * 32, torch.int64)
-        stored = self._forward(x, p, fr, K, B, part, store_last=True, dbg=dbg, shared=shared, psi0=psi0)
+        adjoint, part, wread, gslab = self._head(x, p, K, B, shared_frags, dbg, psi0)
         # Fused readout: the first adjoint pass computes each sample's <Z>, cross entropy and dL/d<Z> from the readout
         # partials, and the gradient reduction sums the clients' loss, hits and readout gradients - one launch fewer
         # per local step.
@@ -784,33 +793,27 @@ class HeaMfmaProgram:
         # records and the reduction are the fused route's, bit for bit.
         ro = None
         mode = self.readout_mode(S, noise)
-        if mode != "kernel":
+        if mode == "kernel":
+            model = (0.0, 0.0, 0, _NO_KEYS, 0)
+            if noise is not None:
+                from .statevec_hip import _keys
+                model = (noise.p01, noise.p10, noise.shots, _keys(keys, noise), int(step))
+            C.readout_ce(part, self.tiles_last, self.C, B, K, yy, ww, p, self.n_theta, expz, wread, loss, correct,
+                         grad, True, *model)
+            adjoint()
+        else:
             rec = self._buf("rorec", S * (2 * self.C + 2), torch.float32)
             ro = [rec, loss, correct]
             if mode == "split":
                 C.hea_readout_rec(part, self.tiles_last, self.C, B, K, yy, ww, p, self.n_theta, expz, wread, rec)
-                self._adjoint(x, p, fr, K, B, stored, wread, gslab, dbg=dbg, shared=shared)
-            else:
-                self._adjoint(x, p, fr, K, B, stored, wread, gslab, readout=(part, yy, ww, expz, rec), dbg=dbg,
-                              shared=shared)
-        else:
-            if noise is None:
-                C.readout_ce(part, self.tiles_last, self.C, B, K, yy, ww, p, self.n_theta, expz, wread, loss,
-                             correct, grad, True, 0.0, 0.0, 0, _NO_KEYS, 0)
-            else:
-                from .statevec_hip import _keys
-                C.readout_ce(part, self.tiles_last, self.C, B, K, yy, ww, p, self.n_theta, expz, wread, loss,
-                             correct, grad, True, noise.p01, noise.p10, noise.shots, _keys(keys, noise), int(step))
-            self._adjoint(x, p, fr, K, B, stored, wread, gslab, dbg=dbg, shared=shared)
-        if adam is None:
-            C.hea_grad_reduce(gslab, self.slab_tiles, self.n_gradops, self.gmeta, B, K, p, grad, p.shape[1],
-                              None, None, ro, self.C, self.n_theta)
-        else:
-            cnt = self._zbuf("adamcnt", K, torch.int32)
+            adjoint(None if mode == "split" else (part, yy, ww, expz, rec))
+        opt, tail = (None, None), ()
+        if adam is not None:
             f = fed if fed is not None else {}
-            C.hea_grad_reduce(gslab, self.slab_tiles, self.n_gradops, self.gmeta, B, K, p, grad, p.shape[1],
-                              adam[0] + [cnt], adam[1], ro, self.C, self.n_theta, f.get("fed"),
-                              bool(f.get("wrap", False)), int(f.get("n_norms", 0)))
+            opt = (adam[0] + [self._zbuf("adamcnt", K, torch.int32)], adam[1])
+            tail = (f.get("fed"), bool(f.get("wrap", False)), int(f.get("n_norms", 0)))
+        C.hea_grad_reduce(gslab, self.slab_tiles, self.n_gradops, self.gmeta, B, K, p, grad, p.shape[1], *opt, ro,
+                          self.C, self.n_theta, *tail)
 
     def _dpsgd_step(self, x, p, yy, ww, K, B, loss, correct, grad, expz, noise, dpsgd, dbg=None, shared_frags=None,
                     psi0=None) -> dict:
@@ -829,27 +832,20 @@ class HeaMfmaProgram:
         clip, sigma, lot = float(dpsgd["clip"]), float(dpsgd["sigma"]), float(dpsgd["lot"])
         if not (clip > 0 and sigma >= 0 and lot > 0):
             raise ValueError("dpsgd needs clip > 0, sigma >= 0 and lot > 0")
-        kk = dpsgd.get("keys")
+        kk = dpsgd.get("keys") if sigma > 0 else _NO_KEYS
         if sigma > 0:
             if kk is None or tuple(kk.shape) != (K, 2):
                 raise ValueError("dpsgd noise needs the clients' Philox keys as a [K, 2] table")
             kk = kk.to(self.device).long().contiguous()      # (a device table already on the round path: no copy)
-        else:
-            kk = _NO_KEYS
         C = ext()
         S = K * B
         live = (ww > 0).float()
-        shared = shared_frags is not None
-        fr = shared_frags if shared else self._frags(p, K)
-        part = self._buf("part", S * self.tiles_last * self.C, torch.float32)
-        wread = self._buf("wread", S * self.C, torch.float32)
-        gslab = self._buf("gslab", S * self.slab_tiles * self.n_gradops * 32, torch.int64)
+        adjoint, part, wread, gslab = self._head(x, p, K, B, shared_frags, dbg, psi0)
         rec = self._buf("rorec", S * (2 * self.C + 2), torch.float32)
         norm = self._buf("dpnorm", S, torch.float64)
         cfac = self._buf("dpc", S, torch.float64)
-        stored = self._forward(x, p, fr, K, B, part, store_last=True, dbg=dbg, shared=shared, psi0=psi0)
         C.hea_readout_rec(part, self.tiles_last, self.C, B, K, yy, live, p, self.n_theta, expz, wread, rec)
-        self._adjoint(x, p, fr, K, B, stored, wread, gslab, dbg=dbg, shared=shared)
+        adjoint()
         C.hea_dp_norm(gslab, self.slab_tiles, self.n_gradops, self.gmeta, B, K, p, rec, self.C, self.n_theta, clip,
                       norm, cfac)
         C.hea_dp_reduce(gslab, self.slab_tiles, self.n_gradops, self.gmeta, B, K, p, rec, live, cfac, self.C,
