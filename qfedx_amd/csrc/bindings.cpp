@@ -635,6 +635,11 @@ int qfx_dm_gate_bytes();
 int qfx_dm_run(const void* gates, int G, int n, const float* rows, int W, long S, const int* readout, int C,
                const float* superop, void* scratch, float* expz, hipStream_t st);
 int qfx_dm_lds_qubits();
+int qfx_dm_forward_tape(const void* gates, int G, int n, const float* rows, int W, long S, const int* readout, int C,
+                        const float* superop, void* scratch, int n_grad, int J, void* tape, float* expz, hipStream_t st);
+int qfx_dm_adjoint(const void* gates, int G, int n, const float* rows, int W, long S, const int* readout, int C,
+                   const float* superop, int n_grad, int J, const void* tape, void* lam, const float* w, float* gg,
+                   hipStream_t st);
 }
 
 // Exact density-matrix run (density.hip): gates = lowered program bytes (ops/density.py), rows [S, W] slot values,
@@ -663,6 +668,76 @@ void dm_run(torch::Tensor gates, int64_t G, int64_t n, torch::Tensor rows, torch
                    (int)C, noisy ? ptr<float>(superop) : nullptr, global ? scratch.data_ptr() : nullptr,
                    ptr<float>(expz), cur_stream()),
         "qfx_dm_run");
+}
+
+// The checks the two reverse-sweep launches share (density_adj.hip): the program, the rows, the channel and the tape
+// [S, J, 4^n] complex64.  Returns whether the channel is present.
+static bool dm_vjp_checks(const char* who, const torch::Tensor& gates, int64_t G, int64_t n, const torch::Tensor& rows,
+                          const torch::Tensor& readout, const torch::Tensor& superop, int64_t n_grad, int64_t J,
+                          const torch::Tensor& tape) {
+  const std::string w(who);
+  need(gates, torch::kInt32, "gates");
+  need(rows, torch::kFloat32, "rows");
+  need(readout, torch::kInt32, "readout");
+  if (G < 0 || gates.numel() * 4 < G * qfx_dm_gate_bytes()) throw std::invalid_argument(w + ": gate table too small");
+  if (rows.dim() != 2 || rows.size(0) < 1) throw std::invalid_argument(w + ": rows must be [S >= 1, W]");
+  if (n < 1 || n > 10) throw std::invalid_argument(w + ": 1 <= n <= 10");
+  if (readout.numel() < 1 || readout.numel() > 16) throw std::invalid_argument(w + ": 1 <= C <= 16 readout qubits");
+  if (n_grad < 0 || n_grad > rows.size(1)) throw std::invalid_argument(w + ": n_grad must lie in [0, W]");
+  const bool noisy = superop.defined() && superop.numel() > 0;
+  if (noisy) {
+    need(superop, torch::kFloat32, "superop");
+    if (superop.numel() != 32) throw std::invalid_argument(w + ": superop must be 4 x 4 complex");
+  }
+  if (J < 0) throw std::invalid_argument(w + ": J < 0");
+  if (J > 0) {
+    need(tape, torch::kComplexFloat, "tape");
+    if (tape.numel() < rows.size(0) * J * (int64_t(1) << (2 * n))) throw std::invalid_argument(w + ": tape too small");
+  }
+  return noisy;
+}
+
+// Forward sweep with tape (density_adj.hip): dm_run's arguments, then n_grad (slots [0, n_grad) are differentiated), J
+// (the number of parametrised one-qubit gates on such slots) and tape [S, J, 4^n] complex64
+void dm_forward_tape(torch::Tensor gates, int64_t G, int64_t n, torch::Tensor rows, torch::Tensor readout,
+                     torch::Tensor superop, torch::Tensor scratch, int64_t n_grad, int64_t J, torch::Tensor tape,
+                     torch::Tensor expz) {
+  const bool noisy = dm_vjp_checks("dm_forward_tape", gates, G, n, rows, readout, superop, n_grad, J, tape);
+  need(expz, torch::kFloat32, "expz");
+  const int64_t S = rows.size(0), C = readout.numel();
+  if (expz.numel() < S * C) throw std::invalid_argument("dm_forward_tape: expz too small");
+  const bool global = n > qfx_dm_lds_qubits();
+  if (global) {
+    need(scratch, torch::kComplexFloat, "scratch");
+    if (scratch.numel() < S * (int64_t(1) << (2 * n))) throw std::invalid_argument("dm_forward_tape: scratch too small");
+  }
+  check(qfx_dm_forward_tape(gates.data_ptr(), (int)G, (int)n, ptr<float>(rows), (int)rows.size(1), (long)S,
+                            ptr<int>(readout), (int)C, noisy ? ptr<float>(superop) : nullptr,
+                            global ? scratch.data_ptr() : nullptr, (int)n_grad, (int)J, J > 0 ? tape.data_ptr() : nullptr,
+                            ptr<float>(expz), cur_stream()),
+        "qfx_dm_forward_tape");
+}
+
+// Backward sweep (density_adj.hip): w [S, C] = d<O>/d<Z_c>, lam [S, 4^n] complex64 (n > LDS qubits), gg [S, G] receives
+// d<O>/d(angle) per gate (0 for gates that are not differentiated)
+void dm_adjoint(torch::Tensor gates, int64_t G, int64_t n, torch::Tensor rows, torch::Tensor readout, torch::Tensor superop,
+                int64_t n_grad, int64_t J, torch::Tensor tape, torch::Tensor lam, torch::Tensor w, torch::Tensor gg) {
+  const bool noisy = dm_vjp_checks("dm_adjoint", gates, G, n, rows, readout, superop, n_grad, J, tape);
+  need(w, torch::kFloat32, "w");
+  need(gg, torch::kFloat32, "gg");
+  const int64_t S = rows.size(0), C = readout.numel();
+  if (w.numel() < S * C) throw std::invalid_argument("dm_adjoint: w too small");
+  if (gg.numel() < S * G) throw std::invalid_argument("dm_adjoint: gg too small");
+  const bool global = n > qfx_dm_lds_qubits();
+  if (global) {
+    need(lam, torch::kComplexFloat, "lam");
+    if (lam.numel() < S * (int64_t(1) << (2 * n))) throw std::invalid_argument("dm_adjoint: lam too small");
+  }
+  check(qfx_dm_adjoint(gates.data_ptr(), (int)G, (int)n, ptr<float>(rows), (int)rows.size(1), (long)S, ptr<int>(readout),
+                       (int)C, noisy ? ptr<float>(superop) : nullptr, (int)n_grad, (int)J,
+                       J > 0 ? tape.data_ptr() : nullptr, global ? lam.data_ptr() : nullptr, ptr<float>(w), ptr<float>(gg),
+                       cur_stream()),
+        "qfx_dm_adjoint");
 }
 void register_hea(pybind11::module& m);
 void register_hea_amp(pybind11::module& m);
@@ -709,6 +784,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dm_run", &dm_run, "exact density-matrix simulation of a lowered noisy program (one workgroup per row)");
   m.def("dm_gate_bytes", []() { return qfx_dm_gate_bytes(); });
   m.def("dm_lds_qubits", []() { return qfx_dm_lds_qubits(); });
+  m.def("dm_forward_tape", &dm_forward_tape, "density-matrix forward sweep that tapes rho in front of every differentiated gate");
+  m.def("dm_adjoint", &dm_adjoint, "density-matrix backward sweep: per-gate angle gradients from the tape");
   register_hea(m);
   register_hea_amp(m);
   register_mps(m);

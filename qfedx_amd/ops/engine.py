@@ -10,6 +10,9 @@ Backends:
   * ``mps``   - batched matrix-product-state network (``quantum/mps.py``) for qubit counts past
                 statevector memory (ROADMAP.md:85-87); ``adjoint`` = reverse-mode AD through the exact
                 network, or parameter shift when the bond bound exceeds ``mps_chi``
+  * ``density`` - exact density matrices with the Kraus gate channel (``ops/density.py``, <= 10 qubits); ``adjoint``
+                (and ``autograd``) = its forward sweep with tape + backward sweep when the readout is exact
+                (``noise.shots`` = 0), parameter shift under shots or with ``QFEDX_DM_ADJOINT=0``
 
 Gradient methods (ROADMAP.md:23,38,130-135): ``adjoint`` (default; 1 forward + 1 reverse sweep),
 ``param_shift`` (2 shifted circuits per rotation gate, batched; on the MFMA engine the same shot-sampled
@@ -338,8 +341,11 @@ class VQCEngine:
         if method == "autograd" and self.backend == "mps":
             method = "adjoint"               # the MPS adjoint IS reverse-mode AD through the network
         if method in ("adjoint", "autograd") and self.backend == "density":
-            # mixed states: the parameter-shift rule holds for exp(-i theta P / 2) rotations with channels that do
-            # not depend on theta in between; the statevector adjoint does not apply
+            # mixed states: one forward sweep with tape + one backward sweep (DensityProgram.vjp) differentiate the
+            # exact expectation; under shots (a sampled readout) or QFEDX_DM_ADJOINT=0 the parameter-shift rule, which
+            # holds for exp(-i theta P / 2) rotations with channels that do not depend on theta in between
+            if os.environ.get("QFEDX_DM_ADJOINT", "1") != "0" and (self.noise is None or self.noise.shots <= 0):
+                return self._density_adjoint(xang, y, wmask, params, readout_keys, step, init)
             method = "param_shift"
         if method == "autograd":
             return self._autograd(xang, y, wmask, params, init)
@@ -405,6 +411,39 @@ class VQCEngine:
                 raise ValueError(f"unknown grad method '{method}'")
         grad = torch.cat([gth, ga, gb], -1)
         return {"loss": loss, "grad": grad, "correct": correct, "expz": expz}
+
+    @torch.no_grad()
+    def _density_adjoint(self, xang, y, wmask, params, readout_keys, step, init=None) -> dict:
+        """Density simulator, exact readout: <Z> and the per-gate gradients of the cross entropy from one forward and
+        one backward sweep per sample (ops/density.py ``vjp``), chunked so that the tape fits ``state_budget_bytes``."""
+        if init is not None:
+            raise ValueError("the density-matrix simulator starts from |0><0| (angle feature maps)")
+        spec = self.spec
+        th, a, b = spec.split(params)
+        K, B, _ = xang.shape
+        P = spec.n_theta
+        # straight-through d<Z>_noisy / d<Z>, as on the statevector adjoint
+        keep = 1.0 if self.noise is None else 1.0 - self.noise.p01 - self.noise.p10
+        yr, wr = y.reshape(-1, 1), wmask.reshape(-1, 1)
+        whole = []                  # (expz, ce_readout(expz)) of the step when one chunk holds every row
+
+        def w_rows(z, lo, hi):      # dL/d<Z> of sample rows lo..hi
+            if hi - lo == K * B:
+                expz = self._readout(z.reshape(K, B, -1), readout_keys, step)
+                whole.append((expz, ce_readout(expz, y, wmask, a, b)))
+                return whole[0][1][1].reshape(K * B, -1) * keep
+            k = torch.arange(lo, hi, device=z.device) // B         # each row is a one-sample batch of its client
+            zz = self._readout(z.unsqueeze(1), readout_keys, step)
+            return ce_readout(zz, yr[lo:hi], wr[lo:hi], a[k], b[k])[1].squeeze(1) * keep
+
+        z, gg = self.prog.vjp(self._rows(xang, th), w_rows, P, budget=self.state_budget_bytes())
+        if not whole:
+            expz = self._readout(z.reshape(K, B, -1), readout_keys, step)
+            whole.append((expz, ce_readout(expz, y, wmask, a, b)))
+        expz, (loss, _, ga, gb, correct) = whole[0]
+        gs = slot_grads(gg, self.ops, self.coef, self.n_slots)[:, :P]
+        gth = gs.reshape(K, B, P).sum(1).float()
+        return {"loss": loss, "grad": torch.cat([gth, ga, gb], -1), "correct": correct, "expz": expz}
 
     def _param_shift(self, rows: torch.Tensor, w: torch.Tensor, K: int, B: int,
                      chunk: int = 32, init: Optional[torch.Tensor] = None) -> torch.Tensor:
