@@ -67,7 +67,10 @@ class TrainConfig:
     local_steps: int = 0                # if >0, overrides local_epochs with a fixed step count
     learning_rate: float = 0.05
     batch_size: int = 32
-    optimizer: str = "adam"             # adam | sgd | spsa
+    optimizer: str = "adam"             # adam | sgd | spsa | qng (quantum natural gradient: the angle gradient
+                                        # preconditioned by the block-diagonal Fubini-Study metric, ops/qng.py; VQC
+                                        # on the statevector simulator, no gate noise, no privacy.level=record)
+    qng_damping: float = 1e-3           # lambda > 0 in (G + lambda I)^{-1} grad of the qng step
     momentum: float = 0.9
     grad_method: str = "adjoint"        # adjoint | param_shift | spsa | autograd
     client_fraction: float = 1.0        # ROADMAP:35,106 client sampling

@@ -739,6 +739,74 @@ void dm_adjoint(torch::Tensor gates, int64_t G, int64_t n, torch::Tensor rows, t
                        cur_stream()),
         "qfx_dm_adjoint");
 }
+
+// ---- quantum natural gradient (qng.hip) ----------------------------------------------------------------------------
+extern "C" {
+int qfx_qng_tile_rec();
+long qfx_qng_tiles(int n);
+int qfx_launch_qng_corr(const void* states, long S, int n, float* trec, double* rec, long rec_stride, hipStream_t st);
+int qfx_launch_qng_blocks(const double* rec, const float* wmask, int K, int B, int nblk, int n, double* out,
+                          hipStream_t st);
+int qfx_launch_qng_step(const double* rec, const float* wmask, int K, int B, int nblk, int n, const float* grad,
+                        const float* active, float* params, int P, double lr, double damping, hipStream_t st);
+}
+
+// <Z_i>, <Z_i Z_j> of states [S, 2^n] complex64 into rec[row0 + s, cut, :] of rec [rows, nblk, n (n + 1) / 2] float64;
+// trec: float32 scratch of S * qng_tiles(n) * qng_tile_rec() entries
+void qng_corr(torch::Tensor states, int64_t n, torch::Tensor trec, torch::Tensor rec, int64_t row0, int64_t cut) {
+  need(states, torch::kComplexFloat, "states");
+  need(trec, torch::kFloat32, "trec");
+  need(rec, torch::kFloat64, "rec");
+  if (n < 1 || n > 32) throw std::invalid_argument("qng_corr: 1 <= n <= 32");
+  if (states.dim() != 2 || states.size(1) != (int64_t(1) << n)) throw std::invalid_argument("qng_corr: states [S, 2^n]");
+  const int64_t S = states.size(0), R = n * (n + 1) / 2;
+  if (reinterpret_cast<uintptr_t>(states.data_ptr()) % 16) throw std::invalid_argument("qng_corr: states not 16-byte aligned");
+  if (rec.dim() != 3 || rec.size(2) != R || row0 < 0 || row0 + S > rec.size(0) || cut < 0 || cut >= rec.size(1))
+    throw std::invalid_argument("qng_corr: rec [rows, nblk, n (n + 1) / 2] does not hold rows row0 .. row0 + S of the cut");
+  if (trec.numel() < S * qfx_qng_tiles((int)n) * qfx_qng_tile_rec()) throw std::invalid_argument("qng_corr: trec too small");
+  check(qfx_launch_qng_corr(states.data_ptr(), (long)S, (int)n, ptr<float>(trec),
+                            rec.data_ptr<double>() + (row0 * rec.size(1) + cut) * R, (long)(rec.size(1) * R),
+                            cur_stream()),
+        "qfx_qng_corr");
+}
+
+static void qng_rec_checks(const char* who, const torch::Tensor& rec, const torch::Tensor& wmask, int64_t n) {
+  const std::string w(who);
+  need(rec, torch::kFloat64, "rec");
+  need(wmask, torch::kFloat32, "wmask");
+  if (n < 1 || n > 32) throw std::invalid_argument(w + ": 1 <= n <= 32");
+  if (wmask.dim() != 2 || rec.dim() != 3 || rec.size(0) != wmask.numel() || rec.size(2) != n * (n + 1) / 2)
+    throw std::invalid_argument(w + ": rec [K * B, nblk, n (n + 1) / 2] float64, wmask [K, B]");
+}
+
+// G [K, nblk, n, n] float64: the clients' metric blocks (mean over live samples), no damping
+void qng_blocks(torch::Tensor rec, torch::Tensor wmask, int64_t n, torch::Tensor out) {
+  qng_rec_checks("qng_blocks", rec, wmask, n);
+  need(out, torch::kFloat64, "out");
+  const int64_t K = wmask.size(0), B = wmask.size(1), nblk = rec.size(1);
+  if (out.numel() != K * nblk * n * n) throw std::invalid_argument("qng_blocks: out [K, nblk, n, n]");
+  check(qfx_launch_qng_blocks(ptr<double>(rec), ptr<float>(wmask), (int)K, (int)B, (int)nblk, (int)n, ptr<double>(out),
+                              cur_stream()),
+        "qfx_qng_blocks");
+}
+
+// params [K, P] -= lr (G + damping I)^{-1} grad per block on active rows, plain step on the entries past n nblk
+void qng_step(torch::Tensor rec, torch::Tensor wmask, int64_t n, torch::Tensor grad, torch::Tensor active,
+              torch::Tensor params, double lr, double damping) {
+  qng_rec_checks("qng_step", rec, wmask, n);
+  need(grad, torch::kFloat32, "grad");
+  need(active, torch::kFloat32, "active");
+  need(params, torch::kFloat32, "params");
+  const int64_t K = wmask.size(0), B = wmask.size(1), nblk = rec.size(1);
+  if (params.dim() != 2 || params.size(0) != K || grad.sizes() != params.sizes() || active.numel() != K ||
+      params.size(1) < n * nblk)
+    throw std::invalid_argument("qng_step: params / grad [K, P >= n nblk], active [K]");
+  if (!(damping > 0.0)) throw std::invalid_argument("qng_step: damping must be > 0");
+  check(qfx_launch_qng_step(ptr<double>(rec), ptr<float>(wmask), (int)K, (int)B, (int)nblk, (int)n, ptr<float>(grad),
+                            ptr<float>(active), ptr<float>(params), (int)params.size(1), lr, damping, cur_stream()),
+        "qfx_qng_step");
+}
+
 void register_hea(pybind11::module& m);
 void register_hea_amp(pybind11::module& m);
 void register_mps(pybind11::module& m);
@@ -786,6 +854,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dm_lds_qubits", []() { return qfx_dm_lds_qubits(); });
   m.def("dm_forward_tape", &dm_forward_tape, "density-matrix forward sweep that tapes rho in front of every differentiated gate");
   m.def("dm_adjoint", &dm_adjoint, "density-matrix backward sweep: per-gate angle gradients from the tape");
+  m.def("qng_corr", &qng_corr, "<Z_i>, <Z_i Z_j> records of complex64 states (one sweep, Walsh-Hadamard tiles)");
+  m.def("qng_tiles", [](int64_t n) { return (int64_t)qfx_qng_tiles((int)n); });
+  m.def("qng_tile_rec", []() { return qfx_qng_tile_rec(); });
+  m.def("qng_blocks", &qng_blocks, "Fubini-Study metric blocks of every client from the per-sample records");
+  m.def("qng_step", &qng_step, "damped natural-gradient step: per-block Cholesky solve in LDS, in place");
   register_hea(m);
   register_hea_amp(m);
   register_mps(m);

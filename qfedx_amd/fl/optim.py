@@ -8,6 +8,10 @@ On GPU the update runs as one fused kernel over all clients (``qfx_adam_kernel``
 ``qfx_sgdm_kernel`` in ``csrc/train_kernels.hip``; the per-client step counter ping-pongs between two
 buffers so the counter update needs no launch of its own); the torch version is the CPU path / oracle.
 Rows with ``active[k] == 0`` are left untouched (clients whose local epochs are exhausted).
+
+``qng`` is the quantum natural gradient (``ops/qng.py``): every step preconditions the angle gradient with the
+block-diagonal Fubini-Study metric the caller hands to ``step(metric=...)``, damped by ``damping``; the readout entries
+take the plain step.  It keeps no momentum and no state between steps (``csrc/qng.hip qng_step`` on GPU, one launch).
 """
 from __future__ import annotations
 
@@ -18,8 +22,16 @@ import torch
 
 class BatchedOptimizer:
     def __init__(self, kind: str, shape, device, lr: float, momentum: float = 0.9,
-                 betas=(0.9, 0.999), eps: float = 1e-8, backend: str = "torch", zero_init: bool = True):
+                 betas=(0.9, 0.999), eps: float = 1e-8, backend: str = "torch", zero_init: bool = True,
+                 damping: float = 1e-3, spec=None):
         self.kind = kind.lower()
+        self.damping = float(damping)
+        self.spec = spec                # qng: the VQCSpec whose blocks the metric holds
+        if self.kind == "qng":
+            if not self.damping > 0:
+                raise ValueError(f"train.qng_damping must be > 0, got {damping}")
+            if spec is None:
+                raise ValueError("BatchedOptimizer('qng') needs the model's VQCSpec (spec=...)")
         self.lr = lr
         self.momentum = momentum
         self.b1, self.b2 = betas
@@ -95,14 +107,19 @@ class BatchedOptimizer:
 
     @torch.no_grad()
     def step(self, params: torch.Tensor, grads: torch.Tensor, active: Optional[torch.Tensor] = None,
-             last: bool = False) -> None:
+             last: bool = False, metric=None) -> None:
         """One update of every active client row.  ``last``: no later step of this round reads the optimizer
-        state (it is reset by the next ``init_round``), so the HIP SGD-momentum path skips storing its buffer."""
+        state (it is reset by the next ``init_round``), so the HIP SGD-momentum path skips storing its buffer.
+        ``metric`` (qng only): the clients' metric at ``params`` - blocks [K, 2L, n, n] on the torch backend, the
+        per-sample records of ``VQCEngine.metric_records`` on HIP."""
         if active is None:
             active = torch.ones(params.shape[0], device=params.device)
         active = active.to(params.dtype)
         if not self._fresh:
             raise RuntimeError("BatchedOptimizer(zero_init=False): call init_round() or reset() first")
+        if self.kind == "qng":
+            self._qng_step(params, grads, active, metric)
+            return
         if self.backend == "hip":
             from ..ops import fedavg_hip
             t_in, t_out = self._t[self._phase], self._t[1 - self._phase]
@@ -134,3 +151,18 @@ class BatchedOptimizer:
             params -= a * self.lr * self.m
         else:
             raise ValueError(f"unknown optimizer '{self.kind}'")
+
+    def _qng_step(self, params, grads, active, metric) -> None:
+        if metric is None:
+            raise ValueError("BatchedOptimizer('qng').step needs metric=... (VQCEngine.metric)")
+        if self.backend == "hip":
+            if not isinstance(metric, dict):
+                raise ValueError("the HIP qng step reads the per-sample records of VQCEngine.metric_records")
+            from ..ops._ext import ext
+            if params.dtype != torch.float32 or not params.is_contiguous():
+                raise ValueError("the HIP qng step updates contiguous float32 params in place")
+            ext().qng_step(metric["rec"], metric["wmask"], self.spec.n_qubits, grads.float().contiguous(),
+                           active.float().contiguous(), params, float(self.lr), self.damping)
+            return
+        from ..ops.qng import qng_step_ref
+        qng_step_ref(params, grads, metric, active, self.lr, self.damping, self.spec)

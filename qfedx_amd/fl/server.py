@@ -107,6 +107,8 @@ class FederatedRunner:
         # record-level DP (DP-SGD inside the local steps): the aggregator then neither clips nor noises
         self.record_dp = bool(p.dp) and level == "record"
         self.client_dp = bool(p.dp) and not self.record_dp
+        if str(t.optimizer).lower() == "qng":
+            self._setup_qng()
         if self.record_dp:
             self._setup_record_dp()
         if p.dp and getattr(p, "noise_mode", "local") == "distributed" and not p.secure_agg:
@@ -168,6 +170,33 @@ class FederatedRunner:
         self._counts_dev = self.store.counts.to(torch.float64).to(device)
         # the device round epilogue (HIP, no server optimizer): FedAvg reduce, collective and apply on the device
         self.epilogue = DeviceRoundEpilogue(self) if backend == "hip" and self.server_opt is None else None
+
+    # ------------------------------------------------------------------ quantum natural gradient
+    def _setup_qng(self) -> None:
+        """``train.optimizer: qng``: refuse what the Fubini-Study metric does not cover, naming the config key.  Client
+        level DP and SecAgg stay available: they act on the whole update."""
+        cfg, t = self.cfg, self.cfg.train
+        what = "train.optimizer=qng"
+        if cfg.model.kind != "vqc":
+            raise ValueError(f"{what} preconditions circuit angles: model.kind=vqc only, got {cfg.model.kind!r}")
+        if not float(getattr(t, "qng_damping", 1e-3)) > 0:
+            raise ValueError(f"train.qng_damping must be > 0 (a block is singular whenever its reference state is an "
+                             f"eigenstate of a generator), got {t.qng_damping}")
+        if cfg.noise.kind != "none":
+            raise ValueError(f"{what} needs noise.kind=none, got {cfg.noise.kind!r}: the metric is a pure-state quantity")
+        if self.record_dp:
+            raise ValueError(f"{what} does not combine with privacy.level=record: the metric is computed from the lot's "
+                             "records without clipping or noise, so the step would not be DP (privacy.level=client "
+                             "and privacy.secure_agg act on the whole update and stay available)")
+        from ..ops.qng import refusal
+        why = refusal(self.adapter.spec, getattr(self.adapter, "noise", None),
+                      getattr(self.adapter, "simulator", "statevector"))
+        if why:
+            raise ValueError(why)
+        eng, need = self.adapter.engine, 2 * 8 * (1 << int(cfg.model.n_qubits))
+        if eng.state_budget_bytes() < need:
+            raise ValueError(f"{what} needs two states of one sample in the state budget: model.n_qubits="
+                             f"{cfg.model.n_qubits} needs {need} bytes, the budget is {eng.state_budget_bytes()}")
 
     # ------------------------------------------------------------------ record-level DP
     def _setup_record_dp(self) -> None:

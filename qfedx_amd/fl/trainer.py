@@ -365,8 +365,12 @@ class VQCClientTrainer:
         P = theta.numel()
         params = torch.empty(K, P, dtype=torch.float32, device=self.device)
         opt_kind = "sgd" if cfg.optimizer == "spsa" else cfg.optimizer
+        # quantum natural gradient: the metric at the current params before every step, no optimizer fused into the
+        # engine's launches and no FedAvg tail (the round then always runs eagerly: run_round)
+        qng = opt_kind == "qng"
         opt = BatchedOptimizer(opt_kind, (K, P), self.device, cfg.learning_rate, cfg.momentum,
-                               backend=self.backend, zero_init=False)
+                               backend=self.backend, zero_init=False,
+                               damping=float(getattr(cfg, "qng_damping", 1e-3)), spec=spec if qng else None)
         loss_all = torch.empty(steps, K, dtype=torch.float32, device=self.device)
         correct_all = torch.empty(steps, K, dtype=torch.float32, device=self.device)
         BT = idx_d.shape[-1] * T
@@ -405,13 +409,14 @@ class VQCClientTrainer:
         if dp is not None and float(dp["sigma"]) > 0 and "dpsgd_keys" not in dv:
             raise ValueError("a record-level DP-SGD round needs the clients' noise keys (extra table 'dpsgd_keys')")
         # (a DP-SGD step has no fused Adam, hence no FedAvg tail: the epilogue's reduce runs it)
-        make = getattr(epilogue, "fused_tail", None) if (fused and method == "adjoint" and dp is None) else None
+        make = getattr(epilogue, "fused_tail", None) if (fused and method == "adjoint" and dp is None
+                                                         and not qng) else None
         ft = make(dict(dv, loss=loss_all, correct=correct_all), theta, ctx) if make is not None else None
         if upfront:
             m, v, t = opt.init_state()
             # the MFMA engine's first-step fragments come from theta in the same launch (every row starts as theta);
             # the FedAvg tail's all-reduce buffer head is zeroed there too
-            fj = self.engine.prologue_frag_job() if method == "adjoint" and noise is None else None
+            fj = self.engine.prologue_frag_job() if method == "adjoint" and noise is None and not qng else None
             gi = idx_d[:0] if pregathered else idx_d.contiguous()         # steps = 0: no gather blocks
             ext().round_prologue(theta.float().contiguous(), params, m, v, t, X, Y, lid, gi, mode,
                                  float(spec.alpha), xbuf[:0] if pregathered else xbuf, ybuf, frag_job=fj,
@@ -453,6 +458,13 @@ class VQCClientTrainer:
                                                  dpsgd={"clip": dp["clip"], "sigma": dp["sigma"], "step": s,
                                                         "keys": dv.get("dpsgd_keys"), "lot": cfg.batch_size})
                 opt.step(params, res["grad"], act_d[s])
+                continue
+            if qng:
+                metric = self.engine.metric(xang, ws, params, init)
+                res = self.engine.loss_and_grads(xang, yb, ws, params, method, rng_keys=(cfg.seed, round_num, s),
+                                                 readout_keys=ro_keys, step=s, out_loss=loss_all[s],
+                                                 out_correct=correct_all[s], init=init)
+                opt.step(params, res["grad"], act_d[s], metric=metric)
                 continue
             res = self.engine.loss_and_grads(xang, yb, ws, params, method, rng_keys=(cfg.seed, round_num, s),
                                              readout_keys=ro_keys, step=s, out_loss=loss_all[s],
@@ -521,7 +533,8 @@ class VQCClientTrainer:
             self.prefetch_hits += 1
         plan, tabs, cids, common, method = pre.plan, pre.tabs, pre.cids, pre.common, pre.method
         noise = self.engine.noise
-        graphed = self.use_graph and method == "adjoint" and noise is None
+        # (a qng round takes the eager path: its metric pass sizes its sample chunks from the free device memory)
+        graphed = self.use_graph and method == "adjoint" and noise is None and self.cfg.optimizer != "qng"
         if graphed:
             tabs = _pad_clients(tabs, graph_bucket(K, len(store)))
             fit = getattr(self.engine, "fit_tiles", None)

@@ -264,6 +264,61 @@ class VQCEngine:
             res["correct"] = out_correct
         return res
 
+    # ------------------------------------------------------------------ quantum natural gradient metric
+    def _metric_check(self, xang, params, init) -> None:
+        from . import qng
+        sim = self.backend if self.backend in ("mps", "density") else "statevector"
+        why = qng.refusal(self.spec, self.noise, sim)
+        if why:
+            raise ValueError(why)
+        self._check(xang, init)
+        need = 2 * 8 * (1 << self.spec.n_qubits)
+        if self.state_budget_bytes() < need:
+            raise ValueError(f"train.optimizer=qng needs two states of one sample in the state budget: "
+                             f"model.n_qubits={self.spec.n_qubits} needs {need} bytes, the budget is "
+                             f"{self.state_budget_bytes()}")
+        if params.shape[-1] < self.spec.n_theta or params.shape[0] != xang.shape[0]:
+            raise ValueError("metric: params [K, >= n_theta] with one row per client of xang [K, B, F]")
+
+    @torch.no_grad()
+    def metric_records(self, xang: torch.Tensor, wmask: torch.Tensor, params: torch.Tensor,
+                       init: Optional[torch.Tensor] = None) -> dict:
+        """HIP backend: what the QNG step kernel reads - ``rec`` [K * B, 2L, n (n + 1) / 2] float64, every sample's
+        [<P_i> | <P_i P_j> (i < j)] at the 2L cut points of the ansatz (``ops/qng.py``), and ``wmask`` [K, B] float32
+        (live samples: > 0).  The cut-point states come from the fp32 VALU pass kernels whichever engine this is, in
+        sample chunks that fit ``state_budget_bytes``."""
+        from . import qng
+        self._metric_check(xang, params, init)
+        if self.backend != "hip":
+            raise ValueError("metric_records is the HIP backend's form of the metric; use metric_blocks")
+        if getattr(self, "_metric_prog", None) is None:
+            self._metric_prog = qng.MetricProgram(self.spec, self.device)
+        rec = self._metric_prog.records(xang, params[:, :self.spec.n_theta], init, self.state_budget_bytes())
+        return {"rec": rec, "wmask": wmask.reshape(xang.shape[0], xang.shape[1]).float().contiguous()}
+
+    @torch.no_grad()
+    def metric_blocks(self, xang: torch.Tensor, wmask: torch.Tensor, params: torch.Tensor,
+                      init: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The clients' block-diagonal Fubini-Study metric [K, 2L, n, n] float64 at ``params``: per block the mean over
+        the client's live samples (``wmask > 0``) of the sample's block, zero for a client without one."""
+        from . import qng
+        self._metric_check(xang, params, init)
+        K, n, L = xang.shape[0], self.spec.n_qubits, self.spec.n_layers
+        if self.backend == "hip":
+            from ._ext import ext
+            m = self.metric_records(xang, wmask, params, init)
+            out = torch.empty(K, 2 * L, n, n, dtype=torch.float64, device=self.device)
+            ext().qng_blocks(m["rec"], m["wmask"], n, out)
+            return out
+        per = qng.fubini_study_blocks(self.spec, xang, params[:, :self.spec.n_theta], init)
+        return qng.client_blocks(per, wmask.reshape(K, -1))
+
+    def metric(self, xang, wmask, params, init=None):
+        """The metric in the form ``BatchedOptimizer('qng').step(metric=...)`` takes on this backend."""
+        if self.backend == "hip":
+            return self.metric_records(xang, wmask, params, init)
+        return self.metric_blocks(xang, wmask, params, init)
+
     # ------------------------------------------------------------------ record-level DP-SGD
     def _dpsgd(self, xang, y, wmask, params, method, readout_keys, step, out_loss, out_correct, init, shared_frags,
                dpsgd: dict) -> dict:
