@@ -49,7 +49,7 @@ class MpsChainProgram:
         ro = self._buf("ro", S * (max(self.readout) + 1) * 128)
         ext().mps_chain(x, th, B, self.n, self.L, self.feature, self.readout, w.reshape(S, self.C).float().contiguous(),
                         z, g, rp, ro)
-        return z.view(K, B, self.C), g.view(K, B, -1)
+        return z.view(K, B, self.C), g.view(K, B, self.n_theta)
 
     @torch.no_grad()
     def expz(self, xang: torch.Tensor, theta: torch.Tensor) -> torch.Tensor:
@@ -79,7 +79,7 @@ class MpsChainProgram:
                         y.reshape(S).long().contiguous(), wmask.reshape(S).float().contiguous(), self.n_theta, dl,
                         lossv, hitv)
         zk, dlk = z.view(K, B, C), dl.view(K, B, C)
-        grad = torch.cat([g.view(K, B, -1).sum(1), (dlk * zk).sum(1), dlk.sum(1)], -1)
+        grad = torch.cat([g.view(K, B, self.n_theta).sum(1), (dlk * zk).sum(1), dlk.sum(1)], -1)
         return lossv.view(K, B).sum(1), grad, hitv.view(K, B).sum(1), zk
 
     @torch.no_grad()

@@ -93,8 +93,7 @@ def test_mps_mpo_kernel_random_circuits_match_dense(cuda):
     for seed in range(3):
         circ, k = _wide_circuit(n, seed)
         sim = Simulator(circ, ro, backend="mps", device=cuda)
-        if sim.prog.hip_program() is None:
-            continue                                       # a draw wider than bond 16
+        assert sim.prog.hip_program() is not None          # seeds 0, 1, 2 all stay within bond 16
         dense = Simulator(circ, ro)
         g = torch.Generator().manual_seed(seed)
         v = torch.randn(5, k, generator=g) * 2
