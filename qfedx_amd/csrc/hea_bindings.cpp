@@ -383,9 +383,9 @@ void hea_dp_reduce(torch::Tensor gslab, int64_t slab_tiles, int64_t n_gradops, t
 }
 
 // Per-plan pass kernels (hea_spec.cpp).  cfg = [n, t, c, lo, hi, C, gen, load_lam, store_lam, n_regions, H0..H4,
-// bf16, stamps, gate_lo (-1: default)[, obs_load (absent: 0)]]; ops / fidx: the pass program's host tensors.
+// bf16, stamps, gate_lo (-1: default)[, obs_load (absent: 0)[, lean mask (absent: 0)]]]; ops / fidx: the pass program's host tensors.
 qfx::HeaSpecDesc spec_desc(bool adjoint, torch::Tensor ops, torch::Tensor fidx, std::vector<int64_t> cfg) {
-  need(cfg.size() == 18 || cfg.size() == 19, "hea_spec: configuration vector must have 18 or 19 entries");
+  need(cfg.size() >= 18 && cfg.size() <= 20, "hea_spec: configuration vector must have 18 to 20 entries");
   need(ops.dim() == 2 && ops.size(1) == 128 && ops.scalar_type() == torch::kInt32 && !ops.is_cuda() && ops.is_contiguous(),
        "hea_spec: ops must be a contiguous host int32 [nops, 128] tensor");
   need(fidx.scalar_type() == torch::kInt32 && !fidx.is_cuda() && fidx.is_contiguous() && fidx.numel() == 2 * ops.size(0),
@@ -397,6 +397,8 @@ qfx::HeaSpecDesc spec_desc(bool adjoint, torch::Tensor ops, torch::Tensor fidx, 
   for (int b = 0; b < 5; ++b) d.hrow[b] = (int)cfg[10 + b];
   d.bf16 = cfg[15] != 0, d.stamps = cfg[16] != 0, d.gate_lo = (int)cfg[17];
   d.obs_load = cfg.size() > 18 && cfg[18] != 0;
+  d.lean = cfg.size() > 19 ? (int)cfg[19] : 0;
+  need(d.lean >= 0 && d.lean <= 7, "hea_spec: lean mask must be 0..7");
   need(d.n >= 8 && d.n <= 30 && d.t >= 8 && d.t <= 14 && d.t <= d.n && d.c >= 2 && d.c <= d.lo && d.lo <= d.hi &&
        d.hi <= d.n && d.c + d.hi - d.lo == d.t && d.ncls >= 1 && d.ncls <= 8, "hea_spec: bad geometry");
   for (int b = 0; b < 5; ++b) need(d.hrow[b] >= 0 && d.hrow[b] < (1 << (d.t - 5)), "hea_spec: swizzle row past the tile bits");

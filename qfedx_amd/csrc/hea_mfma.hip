@@ -47,6 +47,26 @@ constexpr bool SPEC = true;
 #define QFX_HEA_OBS_LOAD 0
 #endif
 constexpr bool OBS_LOAD = QFX_HEA_OBS_LOAD != 0;
+// QFX_HEA_SPEC_LEAN (prelude, the parts of hea_spec.h HEA_LEAN_* that find work in this pass; absent: none, the kernel
+// of before the knob).  Each part leaves out work the results do not depend on, so they stay bitwise what they were:
+//   1  group_pair_back multiplies by the im-row fragments frag_regs formed, and re-derives none per block
+//   2  hea_spec::NOBAR[o]: op o and the op before it are cross-only gradient ops - neither writes the tile or reads
+//      fragments, each adds to LDS regions of its own by integer atomics and gmeta_s is read behind the final barrier -
+//      so op o starts without an op barrier (never with the ring of regions, whose flush needs every barrier)
+//   4  hea_spec::EARLY_STORE = o: only tile reads follow op o's opening barrier (the readout of a forward pass; the
+//      trailing cross-only ops of an adjoint pass that stores lambda), so the tile is stored there and the stores
+//      drain while those ops run
+#ifndef QFX_HEA_SPEC_LEAN
+#define QFX_HEA_SPEC_LEAN 0
+#endif
+#if QFX_HEA_SPEC_LEAN
+constexpr const int (&LEAN_NOBAR)[hea_spec::NOPS] = hea_spec::NOBAR;
+constexpr int LEAN_EARLY = hea_spec::EARLY_STORE;
+#else
+constexpr int LEAN_NOBAR[hea_spec::NOPS] = {};
+constexpr int LEAN_EARLY = -1;
+#endif
+constexpr bool LEAN_IM = (QFX_HEA_SPEC_LEAN & 1) != 0;
 struct PA : PassArgs {
   static constexpr int n = hea_spec::N, t = hea_spec::T, c = hea_spec::CB, lo = hea_spec::LO, hi = hea_spec::HI;
   static constexpr int n_tiles = hea_spec::NTILES, nops = hea_spec::NOPS, C = hea_spec::NCLS;
@@ -85,6 +105,8 @@ struct OpRec {
 #else
 constexpr bool SPEC = false;
 constexpr bool OBS_LOAD = false;
+constexpr bool LEAN_IM = false;
+constexpr int LEAN_EARLY = -1;
 #define HEA_OP_LOOP
 using PA = PassArgs;
 struct OpRec {
@@ -732,17 +754,19 @@ __device__ __forceinline__ void group_pair_back(uint32_t* tile, const uint4* FX,
   };
   // one transposed un-apply of both states + the cross matrix of the results.  The im-row fragments are formed
   // here from the re rows (frag_regs' identity, 4 VALU each): two groups' full fragment sets held across the block
-  // loop pushed the kernel past 128 VGPRs into scratch.
+  // loop pushed the kernel past 128 VGPRs into scratch.  That was the interpreter, at 125-128 VGPRs; a per-plan kernel
+  // has them to spare and multiplies by frag_regs' own F[1] / F[3] (LEAN_IM: the same words, mul_i being exact).
   auto imrow = [](uint4 v) {        // opaque copy first: hoisted out of the block loop, the im rows stay live again
     __asm__ volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
     return make_uint4(mul_i(v.x), mul_i(v.y), mul_i(v.z), mul_i(v.w));
   };
   auto back = [&](const uint4& Ps, const uint4& Ls, const uint4* F, f4* ac, uint4& Po, uint4& Lo) {
     const f4 z = {0.f, 0.f, 0.f, 0.f};
-    uint4 Fi = imrow(F[0]);
+    uint4 Fi;
+    if constexpr (LEAN_IM) Fi = F[1]; else Fi = imrow(F[0]);
     f4 pr = mfma(Ps, F[0], z), pi = mfma(Ps, Fi, z), lr = mfma(Ls, F[0], z), li = mfma(Ls, Fi, z);
     if (QFX_HEA_GATE_LO) {
-      Fi = imrow(F[2]);
+      if constexpr (LEAN_IM) Fi = F[3]; else Fi = imrow(F[2]);
       pr = mfma(Ps, F[2], pr);
       pi = mfma(Ps, Fi, pi);
       lr = mfma(Ls, F[2], lr);
@@ -1202,14 +1226,18 @@ __device__ __forceinline__ void fwd_pass(const PA& a, int bid) {
       group_pair_fwd<NW, TMAX>(psi_t, F, FY, opw, fo_s[o], lane, wave, nbw);
       st.mark(PH_APPLY);
     } else if (code == OP_READOUT) {
+      // (LEAN_EARLY: the readout only reads the tile, as the store does - the stores drain during the sweep)
+      if (LEAN_EARLY == o && a.store_psi) store_tile<NT>(a, a.psi_out + (size_t)s * N, psi_t, tid, T, h_q, fixed);
       const size_t pidx = ((size_t)s * a.n_tiles + tile_id) * a.C;
       readout_op<NCK, NT>(psi_t, a, opw, tid, lane, wave, T, fixed, red, pidx);
       st.mark(PH_OTHER);
     }
     if constexpr (QFX_HEA_STAMPS) ++st.nops;
   }
-  lds_barrier();
-  if (a.store_psi) store_tile<NT>(a, a.psi_out + (size_t)s * N, psi_t, tid, T, h_q, fixed);
+  if constexpr (LEAN_EARLY < 0) {   // (else stored ahead of the readout, whose LDS hand-off has its own barrier)
+    lds_barrier();
+    if (a.store_psi) store_tile<NT>(a, a.psi_out + (size_t)s * N, psi_t, tid, T, h_q, fixed);
+  }
   st.mark(PH_TAIL);
   st.write(a.dbg, bid, NW, wave, lane);
 }
@@ -1448,10 +1476,18 @@ __device__ __forceinline__ void adj_pass(const PA& a, int bid) {
   for (int o = O0; o < a.nops; ++o) {
     // op o's record and fragments were written during op o - 1; the other buffers were last read at the
     // start of op o - 1, which every wave has finished at this barrier, so op o + 1's go there right away
+#ifdef QFX_HEA_SPEC
+    static_assert(LEAN_EARLY < 0 || LEAN_EARLY >= O0, "the tile store follows a barrier the op loop runs behind");
+    if (o > O0 && !LEAN_NOBAR[o]) {
+#else
     if (o > O0) {
+#endif
       op_barrier(wave);
       st.mark(PH_BAR);
     }
+    // (LEAN_EARLY: op o and every op behind it are cross-only, the lambda words are final - the stores drain while
+    // those ops run; a wave issues them behind the barrier that ended the last op to write the tile)
+    if (LEAN_EARLY == o && a.store_lam) store_lam_il<NT, TB>(a, a.lam_out + (size_t)s * N, tile, tid, T, h_q, fixed);
     if (ring && npend > 0) {                           // one wave per region, the last waves
       for (int q = 0; q < npend; ++q)
         if (wave == NW - 1 - q) flush((pending + q) & 3);
@@ -1570,7 +1606,8 @@ __device__ __forceinline__ void adj_pass(const PA& a, int bid) {
   } else {
     for (int e = tid; e < ngrad * 32; e += NT) reduce_region(e >> 5, e & 31);
   }
-  if (a.store_lam) store_lam_il<NT, TB>(a, a.lam_out + (size_t)s * N, tile, tid, T, h_q, fixed);
+  if constexpr (LEAN_EARLY < 0)
+    if (a.store_lam) store_lam_il<NT, TB>(a, a.lam_out + (size_t)s * N, tile, tid, T, h_q, fixed);
   st.mark(PH_TAIL);
   st.write(a.dbg, bid, NW, wave, lane);
 }

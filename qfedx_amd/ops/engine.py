@@ -94,9 +94,11 @@ class VQCEngine:
             self.hip = None
         elif backend == "hip" and state_dtype in ("mfma", "fp16", "mfma_bf16"):
             # fp16 (or bf16) states + MFMA group unitaries (ops/hea_mfma.py) for the hardware-efficient ansatz
-            from .hea_mfma import SPEC_GEN_ENGINE, HeaMfmaProgram, spec_gen_default
+            from .hea_mfma import (SPEC_GEN_ENGINE, SPEC_LEAN_ENGINE, HeaMfmaProgram, spec_gen_default,
+                                   spec_lean_default)
             self.hip = HeaMfmaProgram(spec, self.device, storage="bf16" if state_dtype == "mfma_bf16" else "fp16",
-                                      spec_gen=spec_gen_default(SPEC_GEN_ENGINE))
+                                      spec_gen=spec_gen_default(SPEC_GEN_ENGINE),
+                                      spec_lean=spec_lean_default(SPEC_LEAN_ENGINE))
             self.prog = TorchProgram(ops, coef, spec.n_qubits, self.device)
         elif backend == "hip":
             from .statevec_hip import HipProgram
@@ -129,7 +131,7 @@ class VQCEngine:
         from .hea_mfma import HeaMfmaProgram
         small = HeaMfmaProgram(self.spec, self.device, tile_bits=13, storage=hip.storage,
                                use_spec=hip.spec_requested,   # (compiles its per-plan kernels now: no graph exists yet)
-                               spec_gen=hip.spec_gen)
+                               spec_gen=hip.spec_gen, spec_lean=hip.spec_lean)
         if small.n_passes != hip.n_passes:
             return False
         small.fused_readout = hip.fused_readout

@@ -100,6 +100,21 @@ def spec_gen_default(unset: bool = False) -> bool:
     return _knob("QFEDX_HEA_SPEC_GEN", bool(unset))
 
 
+def spec_lean_default(unset: int = 0) -> int:
+    """``QFEDX_HEA_SPEC_LEAN`` = a bit mask, 0..7: work the per-plan kernels leave out (csrc/hea_spec.h ``HEA_LEAN_*``).
+    1: adjoint pair ops hold the im-row fragments of their op instead of re-deriving them per block; 2: no op barrier
+    between two gradient ops that only read the tile; 4: a pass's tile store is issued ahead of a read-only tail (the
+    readout of a forward pass, trailing cross-only gradient ops of an adjoint pass).  Every part gives bitwise the same
+    results, and ``0`` compiles exactly the text of before the knob.  Read when a program is built
+    (``HeaMfmaProgram.spec_lean``).  Unset, the caller decides (``unset``): the engine turns on ``SPEC_LEAN_ENGINE``,
+    a program built directly keeps 0 unless it is asked (``spec_lean=``)."""
+    env = os.environ.get("QFEDX_HEA_SPEC_LEAN", "")
+    mask = int(unset) if env == "" else int(env)
+    if not 0 <= mask <= 7:
+        raise ValueError(f"QFEDX_HEA_SPEC_LEAN must be a bit mask 0..7, got {mask}")
+    return mask
+
+
 def ring_fwd_from_adj() -> bool:
     """``QFEDX_HEA_RING_ADJ`` = 13 / 14: a ring program's forward runs the groups of its 2^13-tile plan on widened
     tiles, so the adjoint runs on 2^13 tiles (two workgroups per CU) / the forward runs its own 2^14 plan (fewer group
@@ -131,6 +146,14 @@ OBS_LOAD_DEFAULT = True
 # (profiles/hea_spec_gen_ab.txt): 64 clients 1.583 -> 1.539 (3 x the parent's spread: 0.024, met; pass 0 itself 0.30 ->
 # 0.265 ms per dispatch); 8 clients 0.254 -> 0.247, inside three spreads (0.015).
 SPEC_GEN_ENGINE = True
+# The engine's programs compile their per-plan kernels with the held im-row fragments (spec_lean_default, part 1):
+# bitwise the same results.  Measured, 16q x 3L, clients x 32 samples, ms per round parent -> mask 1, alternating on one
+# box, two boxes (profiles/hea_spec_lean_ab.txt): 64 clients 1.526 -> 1.497 (3 x the parent's spread: 0.006) and 1.491
+# -> 1.468 (0.021), every mask-1 run below every parent run; the adjoint passes 0.604 -> 0.583 and 0.422 -> 0.409 ms per
+# dispatch; 8 clients 0.246 -> 0.240.  Parts 2 (no barrier between cross-only gradient ops) and 4 (tile stores ahead of
+# a read-only tail) did not hold their own - alone 1.526 -> 1.527 and 1.522, and part 4 slowed the pass that stores
+# lambda (0.422 -> 0.430 ms: the store's cost is its issue, LDS reads included, not its drain) - and stay off.
+SPEC_LEAN_ENGINE = 1
 # Ring programs: forward on the 2^13 plan's grouping with a 2^13 adjoint (True) or native 2^14 groups with a 2^14
 # adjoint (False); 16q x 3L: 9 against 8 group ops, both in 3 passes.  Measured, clients x 32 samples, ms per step,
 # alternating x 3 on one box (profiles/hea_ring_plan_ab.txt): 64 clients 2.070 -> 2.021 (every run below every native
@@ -150,7 +173,8 @@ _Call = namedtuple("_Call", "x params fr K B shared dbg")
 
 class HeaMfmaProgram:
     def __init__(self, spec, device, tile_bits: int | None = None, adj_tile_bits: int | None = None,
-                 storage: str = "fp16", use_spec: bool | None = None, spec_gen: bool | None = None):
+                 storage: str = "fp16", use_spec: bool | None = None, spec_gen: bool | None = None,
+                 spec_lean: int | None = None):
         """``storage``: fp16 (default) or bf16 (BASELINE config 2) amplitudes and unitary fragments
         (csrc/hea_mfma_bf16.hip: v_mfma_f32_16x16x32_bf16, fp32 accumulation; 2^-9 per-op state rounding)."""
         if storage not in ("fp16", "bf16"):
@@ -207,6 +231,8 @@ class HeaMfmaProgram:
         self.obs_at_load = obs_load_default()
         # the pass that generates the layer-1 product state gets a per-plan kernel too (False: the interpreter)
         self.spec_gen = spec_gen_default() if spec_gen is None else bool(spec_gen)
+        # work the per-plan kernels leave out, a bit mask (0: the kernels of before the knob)
+        self.spec_lean = spec_lean_default() if spec_lean is None else int(spec_lean)
         # per-plan pass kernels: compiled (or loaded from the cache) and their modules loaded here, never inside a
         # stream capture
         self.spec_fwd, self.spec_adj, self.spec_keys = [-1] * self.n_passes, [-1] * self.n_passes, []
@@ -331,7 +357,8 @@ class HeaMfmaProgram:
         from .. import _build
         return [self.n, p.t, p.c, p.lo, p.hi, self.C, gen, load_lam, store_lam,
                 self.n_regions[j] if adjoint else 0] + [int(h) for h in p.H] + \
-               [int(self.bf16), int(_build.variant() == "stamps"), gate_lo, int(self.obs_at_load)]
+               [int(self.bf16), int(_build.variant() == "stamps"), gate_lo, int(self.obs_at_load)] + \
+               ([int(self.spec_lean)] if self.spec_lean else [])     # (0: the list of before the knob)
 
     def prepare_spec(self) -> bool:
         """Compile (or load from ``QFEDX_JIT_CACHE``) the forward and adjoint kernel of every pass; on a failure warn

@@ -81,7 +81,9 @@ def main():
            "readout_mode": prog.readout_mode(S) if hasattr(prog, "readout_mode") else None,
            # (QFEDX_HEA_OBS_LOAD: the per-plan last adjoint pass seeds lambda in its tile load)
            "obs_at_load": getattr(prog, "obs_at_load", None),
-           "spec_gen": getattr(prog, "spec_gen", None)}
+           "spec_gen": getattr(prog, "spec_gen", None),
+           # (QFEDX_HEA_SPEC_LEAN: the mask of work the per-plan kernels leave out)
+           "spec_lean": getattr(prog, "spec_lean", None)}
 
     def timeit(fn, name, nbytes):
         fn()
